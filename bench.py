@@ -7,7 +7,10 @@ solve of the reduced camera system, back-substitution, and the residual-only
 evaluation of the trial point (dbat_hip_bench_step).  Everything is resident
 in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W [--config C3]
+    python bench.py --gpus N --steps K --warmup W [--config C3] [--dump-outputs DIR]
+
+--steps K timed steps; the result line's ms_per_step is the wall time of one.  --dump-outputs DIR: after the timed
+steps, the step's outputs as DIR/*.npy (dump_outputs); the scenes are seeded, so equal arguments give equal inputs.
 
 --config roma | roma-selfcal | camcal | sxb: the reference's own demo projects (bench/real_scenes.py, fixtures under
 tests/golden) -- the scenes DBAT's only published timings are quoted on; the line then also carries the
@@ -107,10 +110,44 @@ def cpu_baseline(s_main, name_main, budget_s=25.0, others=('C1', 'C2')):
     }
 
 
+DUMP_MAX_ELEMENTS = 1 << 20     # per dumped vector: a longer one is written as a fixed, seeded sample (+ its indices)
+DUMP_SEED = 20241
+
+
+def dump_outputs(h, x0, lam, directory, write):
+    """--dump-outputs DIR: what the timed step computes, as .npy files that two builds can be compared by.  The step is
+    dbat_hip_bench_step at x0 with damping lam -- J'J build + Schur solve + back-substitution (the step p) and the
+    residual of the trial point x0 + p.  bench_step itself hands back only its timers, so the same step is taken once
+    more after the timed region through the calls a caller of this path uses (dbat_hip_linearize_solve at the same point
+    and damping, dbat_hip_residual at x0 + p): the same build, solve and objective kernels on the same inputs.  Every rank
+    calls (the calls are collective on a sharded handle); only rank 0 writes (write=True).  float64; at most
+    DUMP_MAX_ELEMENTS per vector, a seeded sample of a longer one with its indices in <name>_index.npy (float64, exact):
+    32 MB at most in all."""
+    p, st = h.linearize_solve(x0, lam, False)
+    r, f_trial = h.residual(x0 + p)
+    if not write:
+        return None
+    os.makedirs(directory, exist_ok=True)
+    scalars = np.array([st['f'], st['JpJp'], st['rJp'], st['pp'], st['trace'], f_trial], np.float64)
+    written = {'scalars': {'shape': [6], 'fields': ['f', 'JpJp', 'rJp', 'pp', 'trace_JtJ', 'f_trial']}}
+    np.save(os.path.join(directory, 'scalars.npy'), scalars)
+    for name, v in (('step', p), ('trial_residual', r)):
+        v = np.ascontiguousarray(v, np.float64)
+        entry = {'shape': [int(v.size)]}
+        if v.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(v.size, DUMP_MAX_ELEMENTS, replace=False))
+            np.save(os.path.join(directory, name + '_index.npy'), idx.astype(np.float64))
+            v = v[idx]
+            entry['sampled'] = int(v.size)
+        np.save(os.path.join(directory, name + '.npy'), v)
+        written[name] = entry
+    return {'dir': os.path.abspath(directory), 'arrays': written}
+
+
 def error_line(args, msg, **kw):
     """One JSON line in the shape of a result, for a run that could not be measured."""
     out = {'metric': 'LM iterations/sec', 'value': None, 'unit': 'it/s', 'n_gpus': args.gpus, 'steps': args.steps,
-           'warmup': args.warmup, 'higher_is_better': True, 'error': msg}
+           'warmup': args.warmup, 'ms_per_step': None, 'higher_is_better': True, 'error': msg}
     out.update(kw)
     print(json.dumps(out), flush=True)
 
@@ -189,7 +226,12 @@ def main():
                     help='one GPU plays rank 0 of R (its share of the points, its domain of the reduced system, the '
                          'collectives replaced by no-ops): per-rank phase times for the scaling estimate of DESIGN.md 6; '
                          'the numbers of the step are meaningless then and "value" is null')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed step computes (the step, the trial residual, its '
+                         'scalars) to DIR/<name>.npy, float64, at most 32 MB (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args))
@@ -299,7 +341,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
-    ms /= max(args.steps, 1)
+    ms /= args.steps
+    dumped = dump_outputs(h, x0, lam, args.dump_outputs, rank == 0) if args.dump_outputs else None
     # every rank's phase times (ms per step), so that the first real multi-GPU run explains itself: rank 0 prints
     # them with the bytes each all-reduce carried and the rate that implies
     per_rank = None
@@ -545,6 +588,7 @@ def main():
             'roofline': roof, 'roofline_factorisation': roof_chol, 'roofline_step': roof_step, 'hbm_kernels': hbm, 'multi_gpu': multi,
             'solve': solve, 'solve_it_s': solve['it_per_s'] if solve else None, 'solve_reference_demo': solve_ref,
             'host_s': {'scene_generation': t_gen, 'library_load_and_first_use': t_first, 'plan_and_upload': t_plan},
+            'dump_outputs': dumped,
         }
         if world == 1 and not args.no_cpu_baseline and not emu:
             try:

@@ -10,13 +10,17 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
 def _golden_path(name):
-    """Path of a fixture; .xz fixtures are unpacked next to pytest's temp files."""
+    """Path of a fixture; .xz fixtures are unpacked next to pytest's temp files, under a name that carries the hash of
+    the packed file (a copy unpacked from another version of the fixture, or by another user, is never taken for it)."""
     path = os.path.join(GOLDEN, name)
     if os.path.exists(path):
         return path
+    import hashlib
     import lzma
     import tempfile
-    out = os.path.join(tempfile.gettempdir(), 'dbat_amd_golden_' + name)
+    with open(path + '.xz', 'rb') as fh:
+        digest = hashlib.sha256(fh.read()).hexdigest()[:16]
+    out = os.path.join(tempfile.gettempdir(), 'dbat_amd_golden_%d_%s_%s' % (os.getuid(), digest, name))
     if not os.path.exists(out):
         with lzma.open(path + '.xz', 'rb') as fi, open(out + '.part%d' % os.getpid(), 'wb') as fo:
             fo.write(fi.read())
