@@ -24,7 +24,7 @@ if LIB_PATH != os.path.join(_HERE, 'libdbat_hip.so'):
     # never silently: a stale development build must not stand in for the product library in a test or bench run
     sys.stderr.write('[dbat_amd] DBAT_AMD_LIB: loading %s instead of the product library\n' % LIB_PATH)
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 DAMP = {'none': 0, 'gm': 0, 'gna': 1, 'lm': 2, 'lmp': 3}
 
 OK, EINVAL, EUNSUPPORTED, EDEVICE, ENOMEM = 0, -101, -102, -103, -104
@@ -153,6 +153,7 @@ SYMBOLS = {
     'dbat_hip_build_kernel_name': (C.c_int, [_H, C.c_char_p, C.c_int32]),
     'dbat_hip_chol_stats': (C.c_int, [_H, C.POINTER(C.c_int64)]),
     'dbat_hip_posterior_cov': (C.c_int, [_H, _dp, C.c_double, _dp, _dp, _dp, _dp]),
+    'dbat_hip_redundancy': (C.c_int, [_H, _dp, _dp, _dp]),
 }
 DEBUG_SYMBOLS = {
     'dbat_hip_debug_plan_digest': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_uint64), C.c_int32, C.c_char_p, C.c_int32]),
@@ -566,6 +567,17 @@ class Handle:
             L = np.tril(Sinv.reshape(NS, NS).T)
             out.append(L + np.tril(L, -1).T)
         return tuple(out)
+
+    def redundancy(self, x):
+        """Reliability at x (dbat_hip_redundancy): Qvv = I - H of every image point as (3, n_obs) rows r_u, q_uv, r_v
+        (IP column order), and the redundancy numbers of the prior rows (m - 2 n_obs,) in the row order of
+        final_residuals."""
+        x = np.ascontiguousarray(x, float)
+        no = int(self.prob.n_obs)
+        qvv = np.zeros(3 * max(no, 1))
+        rp = np.zeros(max(self.m - 2 * no, 1))
+        check(self.lib.dbat_hip_redundancy(self.h, dptr(x), dptr(qvv), dptr(rp)))
+        return qvv[:3 * no].reshape(3, no, order='F'), rp[:self.m - 2 * no]
 
     def set_x(self, x):
         x = np.ascontiguousarray(x, float)

@@ -458,6 +458,10 @@ struct Core {
             SET_LDS((k_cov_points<4, false>), lds_cov); SET_LDS((k_cov_points<5, false>), lds_cov);
             SET_LDS((k_cov_points<2, true>), lds_cov); SET_LDS((k_cov_points<3, true>), lds_cov);
             SET_LDS((k_cov_points<4, true>), lds_cov); SET_LDS((k_cov_points<5, true>), lds_cov);
+            SET_LDS((k_cov_points<2, false, true>), lds_cov); SET_LDS((k_cov_points<3, false, true>), lds_cov);
+            SET_LDS((k_cov_points<4, false, true>), lds_cov); SET_LDS((k_cov_points<5, false, true>), lds_cov);
+            SET_LDS((k_cov_points<2, true, true>), lds_cov); SET_LDS((k_cov_points<3, true, true>), lds_cov);
+            SET_LDS((k_cov_points<4, true, true>), lds_cov); SET_LDS((k_cov_points<5, true, true>), lds_cov);
         }
         if (use_heavy) {
 #define SET_HVZ(M) SET_LDS((k_heavy_z<M, 6>), heavy_z_lds_bytes(6, 0, true)); SET_LDS((k_heavy_z<M, 14>), heavy_z_lds_bytes(14, P.hv_max_batch_slots, true)); SET_LDS((k_heavy_z<M, 15>), heavy_z_lds_bytes(15, P.hv_max_batch_slots, true))
@@ -1129,11 +1133,13 @@ struct Core {
     }
     // ---- posterior covariance blocks at z (bundle_cov.m): s0^2 * blocks of inv(J'J)
     std::vector<double> cop_tmp;
-    void posterior_cov(double s0, double *hCEO, double *hCIO, double *hCOP, double *hSinv) {
-        // inv(S): on one rank, from the compact nested-dissection factor, only the entries the blocks need (selected inversion,
-        // chol_df.hpp) -- no dense inverse (C4: 7.2 GB and 9 TF of rocsolver_dpotri).  The dense inverse remains for several
-        // ranks, for problems without the compact factor (shared EO blocks, DBAT_HIP_ND_OFF) and for a caller who asks for it.
-        const bool selinv = use_perm && !multi() && !hSinv && dfchol.selinv_supported() && !env_on("DBAT_HIP_COV_DENSE");
+    // The set-up shared by posterior_cov and redundancy: the unscaled, undamped reduced system at z (and V^-1 per
+    // point), factored, and inv(S).  On one rank, from the compact nested-dissection factor, only the entries the blocks
+    // need (selected inversion, chol_df.hpp) -- no dense inverse (C4: 7.2 GB and 9 TF of rocsolver_dpotri).  The dense
+    // inverse remains for several ranks, for problems without the compact factor (shared EO blocks, DBAT_HIP_ND_OFF)
+    // and for a caller who asks for it (want_dense).  Leaves the camera records at z.
+    SinvView inverse_at_z(bool want_dense) {
+        const bool selinv = use_perm && !multi() && !want_dense && dfchol.selinv_supported() && !env_on("DBAT_HIP_COV_DENSE");
         replicate_next = !selinv;                    // (domain sharding: the whole system on every rank for this one)
         try { build(z.p, 0.0, 0); } catch (...) { replicate_next = false; throw; }   // unscaled, undamped reduced system + V^-1 per point
         replicate_next = false;
@@ -1167,8 +1173,12 @@ struct Core {
             SV.dense = S; SV.ld = ldS;
         }
         have_lin = false;
-        const double s02 = s0 * s0;
         prep_cams(z.p);
+        return SV;
+    }
+    void posterior_cov(double s0, double *hCEO, double *hCIO, double *hCOP, double *hSinv) {
+        const SinvView SV = inverse_at_z(hSinv != nullptr);
+        const double s02 = s0 * s0;
         DevBuf<double> dCEO, dCIO, dCOP;
         if (hCEO) dCEO.alloc((size_t)36 * P.nc);
         if (hCIO && P.nIOu > 0) dCIO.alloc((size_t)P.nIOu * P.nIOu);
@@ -1203,6 +1213,51 @@ struct Core {
         if (hCOP)                                    // device blocks are in processing order
             for (int64_t p = 0; p < P.np; ++p)
                 std::copy(cop_tmp.begin() + 9 * (int64_t)P.pt_rank[p], cop_tmp.begin() + 9 * (int64_t)P.pt_rank[p] + 9, hCOP + 9 * p);
+    }
+    // ---- reliability at z: Qvv = I - J inv(J'J) J' on the image rows (2 x 2 per image point, caller's order: r_u, q_uv,
+    // r_v) and the redundancy numbers r = 1 - w_p C(p, p) of the prior rows (dbat_hip_final_residuals' row order)
+    void redundancy(double *hqvv, double *hrp) {
+        const SinvView SV = inverse_at_z(false);
+        const int64_t nprior = (int64_t)P.prior_z.size();
+        DevBuf<double> qvv, dCz, Ccc, gscr, rp;
+        DevBuf<int64_t> pz;
+        qvv.alloc((size_t)3 * std::max<int64_t>(P.no, 1));
+        dCz.alloc((size_t)P.NZ);
+        Ccc.alloc((size_t)P.nc * P.ncolmax * P.ncolmax);
+        HIPCHK(hipMemsetAsync(qvv.p, 0, (size_t)3 * P.no * sizeof(double), stream));
+        HIPCHK(hipMemsetAsync(dCz.p, 0, (size_t)P.NZ * sizeof(double), stream));
+        const int64_t nCcc = (int64_t)P.nc * P.ncolmax * P.ncolmax;
+        if (nCcc > 0) LAUNCHK(k_hat_cam_blocks, dim3((unsigned)cdiv(nCcc, 256)), dim3(256), 0, stream, d, cams.p, SV, Ccc.p);
+        HatOut hat;
+        hat.Ccc = Ccc.p; hat.qvv = qvv.p; hat.dCz = dCz.p;
+        if (ngiant > 0) {
+            gscr.alloc((size_t)(P.giant_start.back() - P.giant_start.front()) * 9);
+            hat.gscr = gscr.p;
+        }
+        const size_t lds_cov = ((size_t)P.BT * P.ncolmax * 3 + (size_t)P.BT * 6) * sizeof(double);
+        if (nb > 0) {
+#define L_HAT(M, IO) LAUNCHK((k_cov_points<M, IO, true>), dim3((unsigned)nb), dim3(P.BT), lds_cov, stream, d, z.p, cams.p, Vinv.p, SV, 1.0, (double *)nullptr, hat)
+            if (P.with_io) { DISPATCH_MODEL(L_HAT, true) } else { DISPATCH_MODEL(L_HAT, false) }
+#undef L_HAT
+        }
+        if (ngiant > 0) {
+#define L_HATG(M, IO) LAUNCHK((k_cov_giant<M, IO, true>), dim3((unsigned)ngiant), dim3(giant_threads), 0, stream, d, z.p, cams.p, Vinv.p, SV, 1.0, (double *)nullptr, hat)
+            if (P.with_io) { DISPATCH_MODEL(L_HATG, true) } else { DISPATCH_MODEL(L_HATG, false) }
+#undef L_HATG
+        }
+        if (multi()) {                               // the other shards' observations and points
+            do_allreduce(qvv.p, 3 * P.no);
+            do_allreduce(dCz.p + P.NS, P.NZ - P.NS);
+        }
+        if (nprior > 0) {
+            rp.alloc((size_t)nprior);
+            pz.alloc((size_t)nprior);
+            HIPCHK(hipMemcpyAsync(pz.p, P.prior_z.data(), (size_t)nprior * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+            LAUNCHK(k_hat_prior, dim3((unsigned)cdiv(nprior, 256)), dim3(256), 0, stream, d, SV, pz.p, nprior, dCz.p, rp.p);
+            HIPCHK(hipMemcpyAsync(hrp, rp.p, (size_t)nprior * sizeof(double), hipMemcpyDeviceToHost, stream));
+        }
+        HIPCHK(hipMemcpyAsync(hqvv, qvv.p, (size_t)3 * P.no * sizeof(double), hipMemcpyDeviceToHost, stream));
+        sync();
     }
     // ||J v||^2 and r'Jv at the linearisation point, ||v||^2 over owned entries
     void jtimes(const double *v, double &JvJv, double &rJv, double &vv) {
@@ -2231,6 +2286,17 @@ int dbat_hip_posterior_cov(dbat_hip_handle *h, const double *x, double sigma0, d
     DeviceGuard dev_guard(c.device);
     c.x_to_z(x, c.z.p);
     c.posterior_cov(sigma0, CEO, CIO, COP, Sinv);
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+int dbat_hip_redundancy(dbat_hip_handle *h, const double *x, double *qvv_ip, double *r_prior) {
+    API_TRY
+    if (!h || !x || !qvv_ip || (!r_prior && !h->core->P.prior_z.empty())) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    Core &c = *h->core;
+    DeviceGuard dev_guard(c.device);
+    c.x_to_z(x, c.z.p);
+    c.redundancy(qvv_ip, r_prior);
     return DBAT_HIP_OK;
     API_CATCH
 }

@@ -171,26 +171,8 @@ def bundle(s, *args, device=None, comm=None, store_trace=True, jacobian=False, d
         else:
             s.post.res.IP = ru[:2 * no].reshape(2, no, order='F') / px[:, s.IP.cam]
         IOix, EOix, OPix = h.index_maps()
-        ofs = 2 * no
-        for nm, ixmap in (('IO', IOix), ('EO', EOix), ('OP', OPix)):
-            val = getattr(s, nm).val
-            rows = slice(0, 6) if nm == 'EO' else slice(None)
-            use = np.asarray(getattr(s.prior, nm).use, bool)[rows]
-            arr = np.full(val[rows].shape, np.nan)
-            if not use.any():                                        # no prior observation of this kind: nothing to place
-                setattr(s.post.res, nm, arr)                         # (the leading-element map below sorts 3 x points entries)
-                continue
-            # prior rows = column-major order of use & leading (buildserialindices.m:138-139,200)
-            flatmap = ixmap.flatten('F')
-            lead = np.zeros(flatmap.shape, bool)
-            valid = np.flatnonzero(flatmap >= 0)
-            _, first = np.unique(flatmap[valid], return_index=True)
-            lead[valid[first]] = True
-            pos = np.flatnonzero(use.flatten('F') & lead)
-            flat = arr.flatten('F')
-            flat[pos] = ru[ofs:ofs + len(pos)]
-            ofs += len(pos)
-            setattr(s.post.res, nm, flat.reshape(arr.shape, order='F'))
+        for nm, arr in _place_prior_rows(s, (IOix, EOix, OPix), ru[2 * no:]).items():
+            setattr(s.post.res, nm, arr)
         E.final = NS(unweighted=NS(r=ru), weighted=NS(r=rw))
         if jacobian and E.code != -4:
             E.final.weighted.J = h.jacobian_csc(x, True)
@@ -238,6 +220,32 @@ def bundle(s, *args, device=None, comm=None, store_trace=True, jacobian=False, d
             _hip.release(h, keep=done)                               # (after an exception: destroyed, not kept)
         else:
             h.close()
+
+
+def _place_prior_rows(s, maps, vals):
+    """The prior rows of a residual-like vector (vals: the rows after the 2 x nObs image rows) placed in the val
+    layout of IO, EO (first six rows) and OP: {'IO': ..., 'EO': ..., 'OP': ...}, NaN where there is no prior row."""
+    out, ofs = {}, 0
+    for nm, ixmap in zip(('IO', 'EO', 'OP'), maps):
+        val = getattr(s, nm).val
+        rows = slice(0, 6) if nm == 'EO' else slice(None)
+        use = np.asarray(getattr(s.prior, nm).use, bool)[rows]
+        arr = np.full(val[rows].shape, np.nan)
+        if not use.any():                                            # no prior observation of this kind: nothing to place
+            out[nm] = arr                                            # (the leading-element map below sorts 3 x points entries)
+            continue
+        # prior rows = column-major order of use & leading (buildserialindices.m:138-139,200)
+        flatmap = ixmap.flatten('F')
+        lead = np.zeros(flatmap.shape, bool)
+        valid = np.flatnonzero(flatmap >= 0)
+        _, first = np.unique(flatmap[valid], return_index=True)
+        lead[valid[first]] = True
+        pos = np.flatnonzero(use.flatten('F') & lead)
+        flat = arr.flatten('F')
+        flat[pos] = vals[ofs:ofs + len(pos)]
+        ofs += len(pos)
+        out[nm] = flat.reshape(arr.shape, order='F')
+    return out
 
 
 CXX_MAX_N = 6000       # unknowns up to which bundle_cov offers the dense matrices 'CXX' / 'COPF' (288 MB)
@@ -338,3 +346,94 @@ def bundle_cov(s, E, *names, device=0):
             C = sp.csc_matrix(D)
         out.append(C)
     return out[0] if len(out) == 1 else tuple(out)
+
+
+R_EPS = 1e-12          # redundancy numbers at or below this: an uncontrolled observation (w, T undefined, mdb infinite)
+
+
+def reliability_critical(alpha0=0.001, beta0=0.80):
+    """Critical values of data snooping: the chi^2(2) quantile 1 - alpha0 (the 2-dof test per image point,
+    -2 ln alpha0 in closed form), the two-sided normal quantile 1 - alpha0/2 and the non-centrality
+    delta0 = z(1 - alpha0/2) + z(beta0) of the minimal detectable blunder (4.13 for 0.001 / 0.80)."""
+    from statistics import NormalDist
+    if not (0 < alpha0 < 1 and 0 < beta0 < 1):
+        raise BadInput('bundle_reliability: alpha0 and beta0 must lie in (0, 1)')
+    z = NormalDist()
+    normal = z.inv_cdf(1.0 - alpha0 / 2.0)
+    return NS(alpha0=float(alpha0), beta0=float(beta0), chi2_2=float(-2.0 * np.log(alpha0)), normal=float(normal),
+              delta0=float(normal + z.inv_cdf(beta0)))
+
+
+def reliability_stats(s, rw, qvv, r_prior, maps, alpha0=0.001, beta0=0.80):
+    """The statistics of bundle_reliability from the pieces of Qvv = I - J inv(J'J) J' (pure host function).
+    rw       (m,) weighted residuals (E.final.weighted.r)
+    qvv      (3, nObs) r_u, q_uv, r_v of every image point (IP column order)
+    r_prior  (m - 2 nObs,) redundancy numbers of the prior rows, in the row order of rw
+    maps     (IOix, EOix, OPix) x index of every IO / EO / OP entry, -1 = not an unknown (Handle.index_maps)
+    Returns the struct bundle_reliability documents."""
+    rw = np.asarray(rw, float)
+    no = s.IP.val.shape[1]
+    qvv = np.asarray(qvv, float).reshape(3, no)
+    r_prior = np.asarray(r_prior, float).ravel()
+    if rw.size != 2 * no + r_prior.size:
+        raise BadInput('reliability_stats: %d residual rows, %d image and %d prior rows' % (rw.size, 2 * no, r_prior.size))
+    crit = reliability_critical(alpha0, beta0)
+    ru, quv, rv = qvv
+    rIP = np.vstack([ru, rv])
+    v = rw[:2 * no].reshape(2, no, order='F')
+    ok = rIP > R_EPS
+    sq = np.sqrt(np.where(ok, rIP, 1.0))
+    w = np.where(ok, v / sq, np.nan)
+    std = np.broadcast_to(np.asarray(s.IP.std, float), (2, no))
+    mdb = np.where(ok, crit.delta0 * std / sq, np.inf)
+    # T = v' Qvv^-1 v, chi^2(2) under H0 (a singular 2 x 2 block: undefined)
+    det = ru * rv - quv * quv
+    okT = ok[0] & ok[1] & (det > R_EPS * ru * rv)
+    dets = np.where(okT, det, 1.0)
+    T = np.where(okT, (rv * v[0] ** 2 - 2.0 * quv * v[0] * v[1] + ru * v[1] ** 2) / dets, np.nan)
+    vp = rw[2 * no:]
+    okp = r_prior > R_EPS
+    wp = np.where(okp, vp / np.sqrt(np.where(okp, r_prior, 1.0)), np.nan)
+    rpl = _place_prior_rows(s, maps, r_prior)
+    wpl = _place_prior_rows(s, maps, wp)
+    out = NS(r=np.concatenate([rIP.flatten('F'), r_prior]),
+             IP=NS(r=rIP, q_uv=quv, w=w, T=T, mdb=mdb),
+             IO=NS(r=rpl['IO'], w=wpl['IO']), EO=NS(r=rpl['EO'], w=wpl['EO']), OP=NS(r=rpl['OP'], w=wpl['OP']),
+             critical=crit)
+    out.total = float(out.r.sum())
+    sel = np.flatnonzero(np.nan_to_num(T, nan=-np.inf) > crit.chi2_2)
+    sel = sel[np.argsort(-T[sel], kind='stable')]
+    op_id = getattr(s.OP, 'id', None)
+    pt = np.asarray(s.IP.pt)[sel]
+    out.suspects = NS(ip=sel, op_id=np.asarray(op_id)[pt] if op_id is not None else pt,
+                      image=np.asarray(s.IP.cam)[sel], T=T[sel], w_u=w[0, sel], w_v=w[1, sel])
+    return out
+
+
+def bundle_reliability(s, E, alpha0=0.001, beta0=0.80, device=0):
+    """Internal reliability of the adjustment at E.x, the last linearisation point of bundle(s, ...) (prior sigma0 = 1:
+    independent of the estimated sigma0).  The hat-matrix blocks come from the device (dbat_hip_redundancy: the Schur
+    pieces of the posterior covariance and a selected inversion of the compact factor), on the handle bundle() left
+    behind; this function only forms the statistics (reliability_stats).  Fields:
+      r         (m,) redundancy numbers r_i = 1 - h_ii, row order of E.final.weighted.r; sum = m - n
+      IP        r (2, nObs), q_uv (nObs,) the off-diagonal of Qvv, w (2, nObs) standardized residuals v / sqrt(r),
+                T (nObs,) v' Qvv^-1 v of every image point (chi^2(2) under H0), mdb (2, nObs) minimal detectable
+                blunder delta0 sigma / sqrt(r) in pixels (IP.std); NaN / inf where r <= 1e-12
+      IO, EO, OP  r and w of the prior rows in the val layout of s.post.res.IO / EO / OP, NaN where there is no prior
+      total     sum of r
+      critical  alpha0, beta0, chi2_2 (chi^2(2) quantile 1 - alpha0), normal (normal quantile 1 - alpha0/2), delta0
+      suspects  image points with T > chi2_2 by T descending: ip (IP column), op_id, image (EO column), T, w_u, w_v
+    A bundle that stopped on a singular design matrix (E.code == -4) has no reliability: BadInput."""
+    if int(getattr(E, 'code', 0)) == -4:
+        raise BadInput('bundle_reliability: the bundle stopped on a singular design matrix (code -4); '
+                       'redundancy numbers need J\'J positive definite')
+    crit = reliability_critical(alpha0, beta0)        # (bad levels fail before any device work)
+    h = _hip.acquire(s, device)          # the handle bundle() left behind, with the values of its result
+    done = False
+    try:
+        qvv, rp = h.redundancy(np.asarray(E.x, float))
+        maps = h.index_maps()
+        done = True
+    finally:
+        _hip.release(h, keep=done)
+    return reliability_stats(s, E.final.weighted.r, qvv, rp, maps, crit.alpha0, crit.beta0)

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DBAT_HIP_ABI_VERSION 4   /* 4: dbat_hip_options grew (trace_fun); dbat_hip_structure_key / dbat_hip_handle_key / dbat_hip_set_values; dbat_hip_bench_step ms[16], dbat_hip_info [24]; 3: dbat_hip_options grew (term_fun, veto_fun); 2: dbat_hip_result grew (stage_s, n_trace_only); dbat_hip_info [16]; dbat_hip_bench_step ms[12] */
+#define DBAT_HIP_ABI_VERSION 5   /* 5: dbat_hip_redundancy; 4: dbat_hip_options grew (trace_fun); dbat_hip_structure_key / dbat_hip_handle_key / dbat_hip_set_values; dbat_hip_bench_step ms[16], dbat_hip_info [24]; 3: dbat_hip_options grew (term_fun, veto_fun); 2: dbat_hip_result grew (stage_s, n_trace_only); dbat_hip_info [16]; dbat_hip_bench_step ms[12] */
 
 /* error returns */
 #define DBAT_HIP_OK            0
@@ -465,6 +465,21 @@ int  dbat_hip_chol_stats(const dbat_hip_handle *h, int64_t *st /*[6]*/);
  * the per-point blocks by the owning rank, and all ranks receive all blocks. */
 int  dbat_hip_posterior_cov(dbat_hip_handle *h, const double *x, double sigma0, double *CEO, double *CIO,
                             double *COP, double *Sinv);
+
+/* Reliability at x (internal reliability of the adjustment; prior sigma0 = 1, independent of the
+ * estimated sigma0): the redundancy numbers r_i = 1 - h_ii, h_ii the diagonal of the hat matrix
+ * J inv(J'J) J' of the weighted system (J the weighted Jacobian incl. prior rows, as for
+ * dbat_hip_posterior_cov).  Same set-up as dbat_hip_posterior_cov (reduced system at x, factor,
+ * selected or dense inverse); the 2 x 2 block Qvv = I - H of every image point comes from the
+ * Schur pieces, never from J C J'.
+ * qvv_ip  [3*n_obs]      per IP column (the caller's order): r_u, q_uv, r_v -- Qvv(0,0), Qvv(0,1), Qvv(1,1)
+ * r_prior [m - 2*n_obs]  r of every prior row, in the row order of dbat_hip_final_residuals
+ *                        (may be NULL when there are no prior rows)
+ * Sum over all m rows: m - n.  If J'J is not positive definite the call fails with DBAT_HIP_EDEVICE and
+ * dbat_hip_last_error() "posterior covariance: the reduced normal matrix is not positive definite"
+ * (as dbat_hip_posterior_cov).  On a sharded handle (collective) every rank computes the blocks of
+ * its own observations and all ranks receive everything. */
+int  dbat_hip_redundancy(dbat_hip_handle *h, const double *x, double *qvv_ip, double *r_prior);
 
 #ifdef __cplusplus
 }
