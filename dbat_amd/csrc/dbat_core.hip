@@ -12,6 +12,8 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <atomic>
 #include <vector>
 
@@ -38,12 +40,23 @@ struct UsageError { std::string msg; };
     } while (0)
 
 // every kernel launch is checked: a launch rejected for its grid, LDS size or resources would
-// otherwise be skipped silently and the loops would carry on with stale buffers
-#define LAUNCHK(...)                                                                       \
-    do {                                                                                   \
-        hipLaunchKernelGGL(__VA_ARGS__);                                                   \
-        HIPCHK(hipGetLastError());                                                         \
-    } while (0)
+// otherwise be skipped silently and the loops would carry on with stale buffers.  (The kernel is a template
+// argument: a launch through a function pointer would call the kernel's host-side handle, not its stub.  Default
+// arguments of a kernel do not carry over: every argument is passed.)
+template <auto K, class... A>
+static void launch(dim3 grid, dim3 block, size_t lds, hipStream_t stream, A &&...args) {
+    hipLaunchKernelGGL(K, grid, block, lds, stream, std::forward<A>(args)...);
+    HIPCHK(hipGetLastError());
+}
+
+// f(std::integral_constant) for the first of the values Vs that v equals -- and for the last one when none does: the
+// fallback of a call site is the last value of its list.  Only the listed values are instantiated.
+template <auto V, auto... Vs, class T, class F>
+static inline void with_value(T v, F &&f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<decltype(V), V>{});
+    else if (v == V) f(std::integral_constant<decltype(V), V>{});
+    else with_value<Vs...>(v, f);
+}
 
 // RAII: make the handle's device current for the duration of an ABI call
 struct DeviceGuard {
@@ -87,14 +100,6 @@ static inline void cpu_relax() {
 #endif
 }
 
-#define DISPATCH_MODEL(KERNEL, ...)                                                          \
-    switch (P.model) {                                                                       \
-        case 2: KERNEL(2, __VA_ARGS__); break;                                               \
-        case 3: KERNEL(3, __VA_ARGS__); break;                                               \
-        case 4: KERNEL(4, __VA_ARGS__); break;                                               \
-        default: KERNEL(5, __VA_ARGS__); break;                                              \
-    }
-
 struct Core {
     Plan P;
     DevProblem d{};
@@ -132,9 +137,11 @@ struct Core {
     int tile_ncx = 6;
     int64_t ntiles = 0;
     size_t lds_tile2 = 0, lds_tile3 = 0;
-    bool use_tile3 = false;
     int tile2_pc = TILE2_PC;
     bool use_tile2 = true;
+    // the kernel of the tiled batches, chosen once in init(): k_build_sig (signature groups, sig_rb row blocks),
+    // k_build_tile3 (fixed IO), k_build_tile2 (self-calibration), or none (nothing tiled)
+    enum class TileRoute { none, sig, tile3, tile2 } route = TileRoute::none;
     DevBuf<int64_t> o_row, batch_start, x2z, giant_start, cm_chunk_start;
     DevBuf<int32_t> cm_pt, cm_chunk_cam, tile_order;
     DevBuf<double> cm_uv, cm_w;
@@ -182,7 +189,7 @@ struct Core {
     int env_tail0 = 0;
     int64_t nb = 0, nobs = 0;
     int grid_obs = 1, grid_z = 1, grid_zs = 1;       // grid_zs: blocks of 1024 threads of the kernels that end in a grid sum
-    size_t lds_build = 0, lds_back = 0;
+    size_t lds_build = 0, lds_back = 0, lds_cov = 0;
     // multi-GPU: the RCCL communicator of this handle's rank (dbat_hip_comm_init), or the
     // caller's all-reduce callback (gloo / host tests)
     ncclComm_t nccl = nullptr;
@@ -190,6 +197,25 @@ struct Core {
     void *allreduce_user = nullptr;
     DevBuf<double> zgather;             // [NZ] owned entries of a z-vector, summed over the ranks
     bool multi() const { return nccl != nullptr || allreduce != nullptr; }
+    // kernels with more than 64 KiB of dynamic LDS must opt in on the device: the ones this handle has opted in, and
+    // at what size (a handle's launches run on its one device; a handle opts in at most 5 kernels)
+    struct { const void *kernel; size_t bytes; } lds_opt_in[8] = {};
+    int n_lds_opt_in = 0;
+    // a kernel launch on the handle's stream
+    template <auto K, class... A>
+    void launch(dim3 grid, dim3 block, size_t lds, A &&...args) {
+        if (lds > 65536) {
+            int i = 0;
+            while (i < n_lds_opt_in && lds_opt_in[i].kernel != (const void *)K) ++i;
+            if (i == n_lds_opt_in || lds_opt_in[i].bytes < lds) {
+                if (i == 8) throw DeviceError{"internal: more kernels with over 64 KiB of LDS than the opt-in table holds"};
+                HIPCHK(hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                lds_opt_in[i] = {(const void *)K, lds};
+                n_lds_opt_in = std::max(n_lds_opt_in, i + 1);
+            }
+        }
+        dbat::launch<K>(grid, block, lds, stream, std::forward<A>(args)...);
+    }
     // linearisation state
     double f_lin = 0, trace_jtj = 0, lambda_lin = 0;
     int scale_lin = 0;
@@ -367,12 +393,20 @@ struct Core {
         gpart.alloc((size_t)8 * std::max<int64_t>(std::max<int64_t>(grid_z, cdiv(P.NS, 256)), 2048));
         lds_build = ((size_t)P.BT * P.ncolmax * 3 + (size_t)P.BT * 18) * sizeof(double);
         lds_back = (size_t)P.BT * 6 * sizeof(double);
+        lds_cov = ((size_t)P.BT * P.ncolmax * 3 + (size_t)P.BT * 6) * sizeof(double);
         // wave-specialised tile kernel: 256-observation batches, 16-point chunks, 2 panels
         tile2_pc = TILE2_PC;
         lds_tile2 = ((size_t)TILE2_NBUF * 3 * tile2_pc * TILE_LD + (size_t)256 * 9 + (size_t)128 * 15 + TILE_LD) * sizeof(double);
+        lds_tile3 = ((size_t)TILE3_NBUF * 3 * TILE3_PC * TILE_LD + (size_t)256 * 9 + (size_t)256 * 9 + TILE_LD) * sizeof(double);
         use_tile2 = P.BT == 256 && P.ncolmax <= 15;      // (the plan does not tile anything else)
+        // fixed IO: the tile kernel with two producer groups (it holds at most 64 batch offsets per tile, the plan's
+        // cap is 48); self-calibration: k_build_tile2
+        if (ntiles <= 0) route = TileRoute::none;
+        else if (use_sig) route = TileRoute::sig;
+        else if (use_tile2 && !P.with_io && tile_ncx == 6) route = TileRoute::tile3;
+        else if (use_tile2 && (tile_ncx == 14 || tile_ncx == 15)) route = TileRoute::tile2;
+        else throw DeviceError{"internal: tiles without a tile kernel"};
         partial.alloc((size_t)4 * std::max<int64_t>(std::max<int64_t>(std::max<int64_t>(nb + ntiles + ngiant + (int64_t)P.sg_chunk.size() / 8, n_cm_chunks_all), 2048), 1));
-        set_lds_limits();
         HIPCHK(hipMemcpy(z.p, P.z0.data(), P.NZ * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemset(dz.p, 0, P.NZ * 8));
         HIPCHK(hipMemset(zt.p, 0, P.NZ * 8));          // (entries of other ranks' domains are never written)
@@ -390,12 +424,11 @@ struct Core {
         if (!uv_pre || nobs == 0) return;
         prep_cams(z.p, cams_f.p);                    // interior orientation: the fixed values
         if (!o_rhs.p) o_rhs.alloc((size_t)2 * nobs);
-#define L_RHS(M, dummy)                                                                                              \
-        LAUNCHK((k_uv_to_rhs<M>), dim3((unsigned)cdiv(nobs, 256)), dim3(256), 0, stream, d.nK, d.nP, cams_f.p, nobs, o_cam.p, o_uv.p, o_rhs.p); \
-        if (n_cm_chunks_all > 0) LAUNCHK((k_uv_to_rhs_cm<M>), dim3((unsigned)n_cm_chunks_all), dim3(256), 0, stream, d.nK, d.nP, cams_f.p, cm_chunk_cam.p, cm_chunk_start.p, cm_uv.p); \
-        if (use_sig && sg_nchunks > 0) LAUNCHK((k_uv_to_rhs_sig<M>), dim3((unsigned)sg_nchunks), dim3(64), 0, stream, d.nK, d.nP, cams_f.p, sg_chunk.p, sg_gcam.p, sg_uv.p)
-        DISPATCH_MODEL(L_RHS, 0)
-#undef L_RHS
+        with_value<2, 3, 4, 5>(P.model, [&](auto M) {
+            launch<k_uv_to_rhs<M>>(dim3((unsigned)cdiv(nobs, 256)), dim3(256), 0, d.nK, d.nP, cams_f.p, nobs, o_cam.p, o_uv.p, o_rhs.p);
+            if (n_cm_chunks_all > 0) launch<k_uv_to_rhs_cm<M>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, d.nK, d.nP, cams_f.p, cm_chunk_cam.p, cm_chunk_start.p, cm_uv.p);
+            if (use_sig && sg_nchunks > 0) launch<k_uv_to_rhs_sig<M>>(dim3((unsigned)sg_nchunks), dim3(64), 0, d.nK, d.nP, cams_f.p, sg_chunk.p, sg_gcam.p, sg_uv.p);
+        });
         d.o_uv = o_rhs.p;
     }
 
@@ -426,61 +459,13 @@ struct Core {
     // grid of the grid-stride observation kernels: one resident round (k_residual: 6 waves/SIMD
     // of 4-wave workgroups on 256 CUs)
     static int env_grid_obs() { return std::min(std::max(1, env_int("DBAT_HIP_GRID_OBS", 1536)), 1 << 20); }
-    // kernels that use more than 64 KB of dynamic LDS must opt in
-    void set_lds_limits() {
-#define SET_LDS(K, BYTES) HIPCHK(hipFuncSetAttribute((const void *)(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)))
-        if (use_tile2) {
-            if (P.with_io) {
-                SET_LDS((k_build_tile2<2, 14, TILE2_PC, TILE2_NBUF>), lds_tile2); SET_LDS((k_build_tile2<3, 14, TILE2_PC, TILE2_NBUF>), lds_tile2);
-                SET_LDS((k_build_tile2<4, 14, TILE2_PC, TILE2_NBUF>), lds_tile2); SET_LDS((k_build_tile2<5, 14, TILE2_PC, TILE2_NBUF>), lds_tile2);
-                SET_LDS((k_build_tile2<2, 15, TILE2_PC, TILE2_NBUF>), lds_tile2); SET_LDS((k_build_tile2<3, 15, TILE2_PC, TILE2_NBUF>), lds_tile2);
-                SET_LDS((k_build_tile2<4, 15, TILE2_PC, TILE2_NBUF>), lds_tile2); SET_LDS((k_build_tile2<5, 15, TILE2_PC, TILE2_NBUF>), lds_tile2);
-            }
-        }
-        lds_tile3 = ((size_t)TILE3_NBUF * 3 * TILE3_PC * TILE_LD + (size_t)256 * 9 + (size_t)256 * 9 + TILE_LD) * sizeof(double);
-        // fixed IO: the variant with two producer groups (it holds at most 64 batch offsets per tile, the plan's
-        // cap is 48); self-calibration: k_build_tile2
-        use_tile3 = use_tile2 && !P.with_io;
-        if (use_sig) {
-#define SET_SIG(M, PW) SET_LDS((k_build_sig<M, 4, 6, PW>), sig_lds_bytes(4, false)); SET_LDS((k_build_sig<M, 5, 6, PW>), sig_lds_bytes(5, false)); \
-                       SET_LDS((k_build_sig<M, 4, 14, PW>), sig_lds_bytes(4, true)); SET_LDS((k_build_sig<M, 5, 14, PW>), sig_lds_bytes(5, true));
-            if (P.uniform_w) { SET_SIG(2, false); SET_SIG(3, false); SET_SIG(4, false); SET_SIG(5, false); }
-            else { SET_SIG(2, true); SET_SIG(3, true); SET_SIG(4, true); SET_SIG(5, true); }
-#undef SET_SIG
-        }
-        if (use_tile3) {
-            SET_LDS((k_build_tile3<2, TILE3_PC, TILE3_NBUF>), lds_tile3); SET_LDS((k_build_tile3<3, TILE3_PC, TILE3_NBUF>), lds_tile3);
-            SET_LDS((k_build_tile3<4, TILE3_PC, TILE3_NBUF>), lds_tile3); SET_LDS((k_build_tile3<5, TILE3_PC, TILE3_NBUF>), lds_tile3);
-        }
-        {
-            const size_t lds_cov = ((size_t)P.BT * P.ncolmax * 3 + (size_t)P.BT * 6) * sizeof(double);
-            SET_LDS((k_cov_points<2, false>), lds_cov); SET_LDS((k_cov_points<3, false>), lds_cov);
-            SET_LDS((k_cov_points<4, false>), lds_cov); SET_LDS((k_cov_points<5, false>), lds_cov);
-            SET_LDS((k_cov_points<2, true>), lds_cov); SET_LDS((k_cov_points<3, true>), lds_cov);
-            SET_LDS((k_cov_points<4, true>), lds_cov); SET_LDS((k_cov_points<5, true>), lds_cov);
-            SET_LDS((k_cov_points<2, false, true>), lds_cov); SET_LDS((k_cov_points<3, false, true>), lds_cov);
-            SET_LDS((k_cov_points<4, false, true>), lds_cov); SET_LDS((k_cov_points<5, false, true>), lds_cov);
-            SET_LDS((k_cov_points<2, true, true>), lds_cov); SET_LDS((k_cov_points<3, true, true>), lds_cov);
-            SET_LDS((k_cov_points<4, true, true>), lds_cov); SET_LDS((k_cov_points<5, true, true>), lds_cov);
-        }
-        if (use_heavy) {
-#define SET_HVZ(M) SET_LDS((k_heavy_z<M, 6>), heavy_z_lds_bytes(6, 0, true)); SET_LDS((k_heavy_z<M, 14>), heavy_z_lds_bytes(14, P.hv_max_batch_slots, true)); SET_LDS((k_heavy_z<M, 15>), heavy_z_lds_bytes(15, P.hv_max_batch_slots, true))
-            SET_HVZ(2); SET_HVZ(3); SET_HVZ(4); SET_HVZ(5);
-#undef SET_HVZ
-        }
-        SET_LDS((k_build<2, false>), lds_build); SET_LDS((k_build<3, false>), lds_build);
-        SET_LDS((k_build<4, false>), lds_build); SET_LDS((k_build<5, false>), lds_build);
-        SET_LDS((k_build<2, true>), lds_build); SET_LDS((k_build<3, true>), lds_build);
-        SET_LDS((k_build<4, true>), lds_build); SET_LDS((k_build<5, true>), lds_build);
-#undef SET_LDS
-    }
 
     // v_mfma_f64_16x16x4_f64 instructions (2048 flops each) that one launch of the tile kernel executes: the symmetric
     // products it really runs, for the roofline entry beside the algorithmic (full product) count
     int64_t tile_kernel_mfma() const {
-        if (!(ntiles > 0 && P.nb_tiled > 0)) return 0;
+        if (route == TileRoute::none) return 0;
         int64_t n = 0;
-        if (use_sig) {
+        if (route == TileRoute::sig) {
             for (int64_t t = 0; t < ntiles; ++t) {
                 const int nio = tile_ncx > 6 ? P.tile_io_start[t + 1] - P.tile_io_start[t] : 0;
                 for (int64_t q = P.sg_tile_chunk0[t]; q < P.sg_tile_chunk0[t + 1]; ++q) {
@@ -492,7 +477,7 @@ struct Core {
             return n;
         }
         // dense 128-row tiles: 36 lower-triangle blocks per k-step, chunks of PC points of every batch
-        const int pc = (use_tile3 && tile_ncx == 6) ? TILE3_PC : tile2_pc;
+        const int pc = route == TileRoute::tile3 ? TILE3_PC : tile2_pc;
         for (int64_t b = 0; b < P.nb_tiled; ++b) {
             const int64_t o1 = P.batch_start[b + 1];
             const int npts = o1 > P.batch_start[b] ? (int)P.o_pidx[o1 - 1] + 1 : 0;
@@ -574,11 +559,11 @@ struct Core {
         if (!multi()) return;
         const int64_t nvec = 3 * P.NS + 8;
         if (!pk.p) pk.alloc((size_t)(pk_s_count + nvec));
-        LAUNCHK(k_pack_envelope, dim3((unsigned)P.NS), dim3(256), 0, stream, S, ldS, (int)P.NS, env_tail0,
+        launch<k_pack_envelope>(dim3((unsigned)P.NS), dim3(256), 0, S, ldS, (int)P.NS, env_tail0,
                            col_bend.p, col_off.p, pk.p, 1);
         HIPCHK(hipMemcpyAsync(pk.p + pk_s_count, g_red, nvec * sizeof(double), hipMemcpyDeviceToDevice, stream));
         do_allreduce(pk.p, pk_s_count + nvec);
-        LAUNCHK(k_pack_envelope, dim3((unsigned)P.NS), dim3(256), 0, stream, S, ldS, (int)P.NS, env_tail0,
+        launch<k_pack_envelope>(dim3((unsigned)P.NS), dim3(256), 0, S, ldS, (int)P.NS, env_tail0,
                            col_bend.p, col_off.p, pk.p, 0);
         HIPCHK(hipMemcpyAsync(g_red, pk.p + pk_s_count, nvec * sizeof(double), hipMemcpyDeviceToDevice, stream));
     }
@@ -594,7 +579,7 @@ struct Core {
     const double *gathered(const double *z_dev) {
         if (!multi()) return z_dev;
         if (!zgather.p) zgather.alloc((size_t)P.NZ);
-        LAUNCHK(k_mask_owned, dim3((unsigned)cdiv(P.NZ, 256)), dim3(256), 0, stream, P.NZ, z_mine.p, z_dev, zgather.p);
+        launch<k_mask_owned>(dim3((unsigned)cdiv(P.NZ, 256)), dim3(256), 0, P.NZ, z_mine.p, z_dev, zgather.p);
         do_allreduce(zgather.p, P.NZ);
         return zgather.p;
     }
@@ -610,21 +595,21 @@ struct Core {
     }
     void prep_cams(const double *zz, CamRec *into = nullptr) {
         if (!into) { into = cams.p; cams_at_lin = false; }      // build() sets it again once zlin == zz
-        LAUNCHK(k_cam_prep, dim3((unsigned)cdiv(P.nc, 64)), dim3(64), 0, stream, d, zz, into);
+        launch<k_cam_prep>(dim3((unsigned)cdiv(P.nc, 64)), dim3(64), 0, d, zz, into);
     }
     void x_to_z(const double *x_host, double *z_dev) {
         // z keeps fixed entries; estimated entries overwritten from x
         HIPCHK(hipMemcpyAsync(z_dev, P.z0.data(), P.NZ * 8, hipMemcpyHostToDevice, stream));
         if (P.n) {
             HIPCHK(hipMemcpyAsync(xbuf.p, x_host, P.n * 8, hipMemcpyHostToDevice, stream));
-            LAUNCHK(k_scatter_x, dim3((unsigned)cdiv(P.n, 256)), dim3(256), 0, stream, P.n, x2z.p, xbuf.p, z_dev);
+            launch<k_scatter_x>(dim3((unsigned)cdiv(P.n, 256)), dim3(256), 0, P.n, x2z.p, xbuf.p, z_dev);
         }
     }
     void z_to_x(const double *z_dev, double *x_host) {     // collective on a sharded handle
         if (!P.n) return;
         stage(4);
         z_dev = gathered(z_dev);
-        LAUNCHK(k_gather_x, dim3((unsigned)cdiv(P.n, 256)), dim3(256), 0, stream, P.n, x2z.p, z_dev, xbuf.p);
+        launch<k_gather_x>(dim3((unsigned)cdiv(P.n, 256)), dim3(256), 0, P.n, x2z.p, z_dev, xbuf.p);
         HIPCHK(hipMemcpyAsync(x_host, xbuf.p, P.n * 8, hipMemcpyDeviceToHost, stream));
         sync();
     }
@@ -650,7 +635,7 @@ struct Core {
         }
         stage(4);
         z_dev = gathered(z_dev);
-        LAUNCHK(k_gather_x, dim3((unsigned)cdiv(P.n, 256)), dim3(256), 0, stream, P.n, x2z.p, z_dev, trace_dev.p + (size_t)P.n * k);
+        launch<k_gather_x>(dim3((unsigned)cdiv(P.n, 256)), dim3(256), 0, P.n, x2z.p, z_dev, trace_dev.p + (size_t)P.n * k);
         if ((int)trace_have.size() <= k) trace_have.resize((size_t)k + 1, 0);
         trace_have[k] = 1;
         trace_n = std::max(trace_n, k + 1);
@@ -676,7 +661,7 @@ struct Core {
     double eval_f_step(const double *x, double alpha, const double *pdir, double *out) {
         stage(3);
         if ((int64_t)cdiv(P.NZ, 256) < P.nc) { axpby(1.0, x, alpha, pdir, out); return eval_f(out, nullptr, nullptr); }
-        LAUNCHK(k_axpby_cams, dim3((unsigned)cdiv(P.NZ, 256)), dim3(256), 0, stream, d, 1.0, x, alpha, pdir, out, cams_f.p);
+        launch<k_axpby_cams>(dim3((unsigned)cdiv(P.NZ, 256)), dim3(256), 0, d, 1.0, x, alpha, pdir, out, cams_f.p);
         return eval_f(out, nullptr, nullptr, true);
     }
     double eval_f(const double *zz, double *r_w_out, double *r_unw_out, bool cams_ready = false) {
@@ -690,21 +675,18 @@ struct Core {
         // the total to the pinned mailbox (one rank) or to scal[0] for the all-reduce.
         // small projects without prior observations: the residual kernel's last block sums up and tells the host itself
         const bool res_tail = n_cm_chunks_all > 0 && n_cm_chunks_all <= 512 && !d.any_prior && !multi() && !r_w_out && !r_unw_out;
-        if (n_cm_chunks_all > 0) {
-#define L_RESCM(M, PRE) LAUNCHK((k_residual_cm<M, PRE>), dim3((unsigned)n_cm_chunks_all), dim3(256), 0, stream, d, zz, cams_f.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p, cm_chunk_cam.p, cm_chunk_start.p, partial.p, \
-                                res_tail ? gctr.p + 1 : (unsigned *)nullptr, scal.p, hpin, res_tail ? ++mb_seq : 0ull)
-            if (uv_pre) { DISPATCH_MODEL(L_RESCM, true) } else { DISPATCH_MODEL(L_RESCM, false) }
-#undef L_RESCM
-        }
-        mark(7);
-        if (r_w_out || r_unw_out) {
-#define L_RES(M, PRE) LAUNCHK((k_residual<M, PRE>), dim3(grid_obs), dim3(256), 0, stream, d, zz, cams_f.p, rpart.p, r_w_out, r_unw_out)
-            if (uv_pre) { DISPATCH_MODEL(L_RES, true) } else { DISPATCH_MODEL(L_RES, false) }
-#undef L_RES
-        }
+        with_value<2, 3, 4, 5>(P.model, [&](auto M) {
+            with_value<false, true>(uv_pre, [&](auto PRE) {
+                if (n_cm_chunks_all > 0)
+                    launch<k_residual_cm<M, PRE>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, d, zz, cams_f.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p,
+                                                  cm_chunk_cam.p, cm_chunk_start.p, partial.p, res_tail ? gctr.p + 1 : (unsigned *)nullptr, scal.p, hpin, res_tail ? ++mb_seq : 0ull);
+                mark(7);
+                if (r_w_out || r_unw_out) launch<k_residual<M, PRE>>(dim3(grid_obs), dim3(256), 0, d, zz, cams_f.p, rpart.p, r_w_out, r_unw_out);
+            });
+        });
         if (!res_tail)
-            LAUNCHK(k_prior_sq, dim3(grid_zs), dim3(1024), 0, stream, d, zz, gpart.p, gctr.p + 1, (const double *)partial.p, n_cm_chunks_all,
-                    scal.p, multi() ? (double *)nullptr : hpin, ++mb_seq);
+            launch<k_prior_sq>(dim3(grid_zs), dim3(1024), 0, d, zz, gpart.p, gctr.p + 1, (const double *)partial.p, n_cm_chunks_all,
+                               scal.p, multi() ? (double *)nullptr : hpin, ++mb_seq);
         double s;
         if (multi()) { do_allreduce(scal.p, 1); read_scal(&s, 1); }
         else { mb_armed = true; sync(); s = hpin[0]; }
@@ -757,14 +739,23 @@ struct Core {
     void det_camera_side() {
         const int nio = (int)P.nIOu;
         const int ncx = det_ncx();
-#define L_DCR(NCXV) LAUNCHK((k_det_cam_reduce<NCXV>), dim3((unsigned)P.nc), dim3(256), 0, stream, d, cams.p, S, g_c, g_red, diagU)
-        if (ncx == 6) L_DCR(6); else if (ncx == 14) L_DCR(14); else L_DCR(15);
-#undef L_DCR
-        if (ncx > 6 && nio > 0) LAUNCHK((k_det_io_reduce<15>), dim3((unsigned)(nio * (nio + 1) / 2 + nio)), dim3(256), 0, stream, d, cams.p, nio, S, g_c, g_red, diagU);
-        if (d.any_prior) LAUNCHK(k_det_prior_sq, dim3(DET_PRIOR_PARTS), dim3(256), 0, stream, d, det_z);
-        LAUNCHK(k_det_rows, dim3((unsigned)cdiv(P.NS, 256)), dim3(256), 0, stream, d, (const double *)diagU);
-        if (ncx == 6) LAUNCHK((k_det_round_cam<6>), dim3((unsigned)P.nc), dim3(256), 0, stream, d, cams.p, 0, S, g_red);
-        else LAUNCHK((k_det_round_cam<15>), dim3((unsigned)P.nc + 1), dim3(256), 0, stream, d, cams.p, nio, S, g_red);
+        with_value<6, 14, 15>(ncx, [&](auto NCX) { launch<k_det_cam_reduce<NCX>>(dim3((unsigned)P.nc), dim3(256), 0, d, cams.p, S, g_c, g_red, diagU); });
+        if (ncx > 6 && nio > 0) launch<k_det_io_reduce<15>>(dim3((unsigned)(nio * (nio + 1) / 2 + nio)), dim3(256), 0, d, cams.p, nio, S, g_c, g_red, diagU);
+        if (d.any_prior) launch<k_det_prior_sq>(dim3(DET_PRIOR_PARTS), dim3(256), 0, d, det_z);
+        launch<k_det_rows>(dim3((unsigned)cdiv(P.NS, 256)), dim3(256), 0, d, (const double *)diagU);
+        if (ncx == 6) launch<k_det_round_cam<6>>(dim3((unsigned)P.nc), dim3(256), 0, d, cams.p, 0, S, g_red);
+        else launch<k_det_round_cam<15>>(dim3((unsigned)P.nc + 1), dim3(256), 0, d, cams.p, nio, S, g_red);
+    }
+
+    // camera side J_c'J_c, J_c'r and squared column norms of the camera-major chunks [q0, q0 + nq)
+    void cam_normal(const double *zz, int64_t q0, int64_t nq, int ncx) {
+        const double *w = P.uniform_w ? (const double *)nullptr : cm_w.p;
+        with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15>(ncx, [&](auto NCX) {
+            if constexpr (NCX == 6)
+                launch<k_cam_normal6<M>>(dim3((unsigned)nq), dim3(256), 0, d, zz, cams.p, cm_pt.p, cm_uv.p, w, cm_chunk_cam.p + q0, cm_chunk_start.p + q0, S, g_c, g_red, diagU);
+            else
+                launch<k_cam_normal<M, NCX>>(dim3((unsigned)nq), dim3(256), 0, d, zz, cams.p, cm_pt.p, cm_uv.p, w, cm_chunk_cam.p + q0, cm_chunk_start.p + q0, S, g_c, g_red, diagU);
+        }); });
     }
 
     // ---- K1: linearise at zz with damping lambda; builds the reduced system.
@@ -782,7 +773,7 @@ struct Core {
         } else {
             // ... and the vectors behind S, and the pivot extremes {min, max} x {points, cameras}
             // ... and the camera records at zz, all in the first launch
-            LAUNCHK(k_envelope_cams, dim3((unsigned)P.NS), dim3(256), 0, stream, d, zz, cams.p, S, ldS, (int)P.NS, env_tail0, col_bend.p, g_red, pivmm.p);
+            launch<k_envelope_cams>(dim3((unsigned)P.NS), dim3(256), 0, d, zz, cams.p, S, ldS, (int)P.NS, env_tail0, col_bend.p, g_red, pivmm.p);
             pivmm_set = true;
         }
         if (!pivmm_set) HIPCHK(hipMemcpyAsync(pivmm.p, hpin + 48, 4 * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -790,45 +781,37 @@ struct Core {
         // -- or all of them when tiling is off -- through k_build
         int64_t npart = 0;
         // deterministic mode off the signature path: no tile kernel, k_build takes every batch
-        const bool det_list = deterministic && !(use_sig && ntiles > 0 && P.nb_tiled > 0);
+        const bool det_list = deterministic && route != TileRoute::sig;
         const int64_t nb_tiled = det_list ? 0 : P.nb_tiled;
         if (deterministic) {
             // the camera side of EVERY observation (tiled or not) from the camera-major kernels, chunk partials summed in order
-#define L_CAMN_ALL(M, NCXV) LAUNCHK((k_cam_normal<M, NCXV>), dim3((unsigned)n_cm_chunks_all), dim3(256), 0, stream, d, zz, cams.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p, cm_chunk_cam.p, cm_chunk_start.p, S, g_c, g_red, diagU)
-#define L_CAMN6_ALL(M, dummy) LAUNCHK((k_cam_normal6<M>), dim3((unsigned)n_cm_chunks_all), dim3(256), 0, stream, d, zz, cams.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p, cm_chunk_cam.p, cm_chunk_start.p, S, g_c, g_red, diagU)
-            const int ncx = det_ncx();
-            if (ncx == 6) { DISPATCH_MODEL(L_CAMN6_ALL, 0) } else if (ncx == 14) { DISPATCH_MODEL(L_CAMN_ALL, 14) } else { DISPATCH_MODEL(L_CAMN_ALL, 15) }
-#undef L_CAMN_ALL
-#undef L_CAMN6_ALL
+            cam_normal(zz, 0, n_cm_chunks_all, det_ncx());
             det_z = zz;
             det_camera_side();
         }
         if (ntiles > 0 && nb_tiled > 0) {
             npart = ntiles;
-#define L_TILE2(M, NCXV) LAUNCHK((k_build_tile2<M, NCXV, TILE2_PC, TILE2_NBUF>), dim3((unsigned)ntiles), dim3(512), lds_tile2, stream, d, zz, cams.p, lambda, scale, S, g_c, g_red, diagU, Vinv.p, gp.p, jn2p.p, partial.p, pivmm.p)
-#define L_CAMN(M, NCXV) LAUNCHK((k_cam_normal<M, NCXV>), dim3((unsigned)n_cm_chunks), dim3(256), 0, stream, d, zz, cams.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p, cm_chunk_cam.p, cm_chunk_start.p, S, g_c, g_red, diagU)
-            if (!deterministic && use_tile2 && tile_ncx <= 15 && n_cm_chunks > 0) {
-                // camera side of the tiled observations: J_c'J_c, J_c'r, squared column norms
-#define L_CAMN6(M, dummy) LAUNCHK((k_cam_normal6<M>), dim3((unsigned)n_cm_chunks), dim3(256), 0, stream, d, zz, cams.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p, cm_chunk_cam.p, cm_chunk_start.p, S, g_c, g_red, diagU)
-                if (tile_ncx == 6) { DISPATCH_MODEL(L_CAMN6, 0) } else if (tile_ncx == 14) { DISPATCH_MODEL(L_CAMN, 14) } else { DISPATCH_MODEL(L_CAMN, 15) }
-#undef L_CAMN6
-            }
-#undef L_CAMN
+            // camera side of the tiled observations: J_c'J_c, J_c'r, squared column norms
+            if (!deterministic && use_tile2 && tile_ncx <= 15 && n_cm_chunks > 0) cam_normal(zz, 0, n_cm_chunks, tile_ncx);
             mark(0);                                 // events around the tile kernel alone (bench roofline)
-#define L_TILE3(M, DUMMY) LAUNCHK((k_build_tile3<M, TILE3_PC, TILE3_NBUF>), dim3((unsigned)ntiles), dim3(768), lds_tile3, stream, d, zz, cams.p, lambda, scale, S, g_red, Vinv.p, gp.p, jn2p.p, partial.p, pivmm.p)
-#define L_SIGW(M, RBV, PW) LAUNCHK((k_build_sig<M, (RBV) % 8, (RBV) / 8, PW>), dim3((unsigned)std::min<int64_t>(ntiles, n_cu)), dim3(64 * sig_waves((RBV) % 8, (RBV) / 8 > 6)), sig_lds_bytes((RBV) % 8, (RBV) / 8 > 6), stream, d, zz, cams.p, lambda, scale, S, g_red, Vinv.p, gp.p, jn2p.p, partial.p, pivmm.p, sg_chunk.p, sg_tile_chunk0.p, sg_lc.p, sg_uv.p, PW ? sg_w.p : (const double *)nullptr, gctr.p + 5)
-#define L_SIG(M, RBV) do { if (P.uniform_w) L_SIGW(M, RBV, false); else L_SIGW(M, RBV, true); } while (0)
-            // (row blocks, camera-side columns) packed into one macro argument: RB + 8 * NCX
-            if (use_sig && tile_ncx == 6 && sig_rb == 4) { DISPATCH_MODEL(L_SIG, 4 + 8 * 6) }
-            else if (use_sig && tile_ncx == 6) { DISPATCH_MODEL(L_SIG, 5 + 8 * 6) }
-            else if (use_sig && sig_rb == 4) { DISPATCH_MODEL(L_SIG, 4 + 8 * 14) }
-            else if (use_sig) { DISPATCH_MODEL(L_SIG, 5 + 8 * 14) }
-            else if (use_tile3 && tile_ncx == 6) { DISPATCH_MODEL(L_TILE3, 0) }
-            else if (use_tile2 && tile_ncx == 14) { DISPATCH_MODEL(L_TILE2, 14) }
-            else if (use_tile2 && tile_ncx == 15) { DISPATCH_MODEL(L_TILE2, 15) }
-            else throw DeviceError{"internal: tiles without a tile kernel"};
+            with_value<2, 3, 4, 5>(P.model, [&](auto M) {
+                if (route == TileRoute::sig) {
+                    with_value<6, 14>(tile_ncx, [&](auto NCX) { with_value<4, 5>(sig_rb, [&](auto RB) { with_value<false, true>(!P.uniform_w, [&](auto PW) {
+                        launch<k_build_sig<M, RB, NCX, PW>>(dim3((unsigned)std::min<int64_t>(ntiles, n_cu)), dim3(64 * sig_waves(RB, NCX > 6)), sig_lds_bytes(RB, NCX > 6),
+                                                            d, zz, cams.p, lambda, scale, S, g_red, Vinv.p, gp.p, jn2p.p, partial.p, pivmm.p, sg_chunk.p, sg_tile_chunk0.p,
+                                                            sg_lc.p, sg_uv.p, PW ? sg_w.p : (const double *)nullptr, gctr.p + 5);
+                    }); }); });
+                } else if (route == TileRoute::tile3) {
+                    launch<k_build_tile3<M, TILE3_PC, TILE3_NBUF>>(dim3((unsigned)ntiles), dim3(768), lds_tile3, d, zz, cams.p, lambda, scale, S, g_red, Vinv.p, gp.p,
+                                                                   jn2p.p, partial.p, pivmm.p);
+                } else {
+                    with_value<14, 15>(tile_ncx, [&](auto NCX) {
+                        launch<k_build_tile2<M, NCX, TILE2_PC, TILE2_NBUF>>(dim3((unsigned)ntiles), dim3(512), lds_tile2, d, zz, cams.p, lambda, scale, S, g_c, g_red,
+                                                                            diagU, Vinv.p, gp.p, jn2p.p, partial.p, pivmm.p);
+                    });
+                }
+            });
             mark(1);
-#undef L_TILE2
         }
         const bool no_tiles = !(ntiles > 0 && nb_tiled > 0);
         if (no_tiles) mark(0);                       // no tile kernel: the events bracket the kernels of the untiled points instead
@@ -836,46 +819,43 @@ struct Core {
         // tiled batches that the deterministic mode keeps off the tile kernels stay with the column lists
         const int64_t nb_lists = use_heavy ? P.nb_tiled : nb;      // batches [nb_tiled, nb_lists) go through k_build
         if (nb_lists > nb_tiled) {
-#define L_BUILD(M, IO) LAUNCHK((k_build<M, IO>), dim3((unsigned)(nb_lists - nb_tiled)), dim3(P.BT), lds_build, stream, d, zz, cams.p, lambda, scale, S, g_c, g_red, diagU, Vinv.p, gp.p, jn2p.p, partial.p + npart, pivmm.p, (int)nb_tiled)
-            if (P.with_io) { DISPATCH_MODEL(L_BUILD, true) } else { DISPATCH_MODEL(L_BUILD, false) }
-#undef L_BUILD
+            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
+                launch<k_build<M, IO>>(dim3((unsigned)(nb_lists - nb_tiled)), dim3(P.BT), lds_build, d, zz, cams.p, lambda, scale, S, g_c, g_red, diagU, Vinv.p, gp.p,
+                                       jn2p.p, partial.p + npart, pivmm.p, (int)nb_tiled);
+            }); });
             npart += nb_lists - nb_tiled;
         }
         if (use_heavy) {
             mark(10);
-            if (!deterministic && n_cm_chunks_all > n_cm_chunks) {
-                // camera side of the untiled observations (deterministic mode: every chunk has been through it above)
-                const unsigned nch = (unsigned)(n_cm_chunks_all - n_cm_chunks);
-#define L_CAMNU(M, NCXV) LAUNCHK((k_cam_normal<M, NCXV>), dim3(nch), dim3(256), 0, stream, d, zz, cams.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p, cm_chunk_cam.p + n_cm_chunks, cm_chunk_start.p + n_cm_chunks, S, g_c, g_red, diagU)
-#define L_CAMN6U(M, dummy) LAUNCHK((k_cam_normal6<M>), dim3(nch), dim3(256), 0, stream, d, zz, cams.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p, cm_chunk_cam.p + n_cm_chunks, cm_chunk_start.p + n_cm_chunks, S, g_c, g_red, diagU)
-                if (tile_ncx == 6) { DISPATCH_MODEL(L_CAMN6U, 0) } else if (tile_ncx == 14) { DISPATCH_MODEL(L_CAMNU, 14) } else { DISPATCH_MODEL(L_CAMNU, 15) }
-#undef L_CAMNU
-#undef L_CAMN6U
-            }
+            // camera side of the untiled observations (deterministic mode: every chunk has been through it above)
+            if (!deterministic && n_cm_chunks_all > n_cm_chunks) cam_normal(zz, n_cm_chunks, n_cm_chunks_all - n_cm_chunks, tile_ncx);
             if (nb > P.nb_tiled) {
-#define L_HVZ(M, NCXV) LAUNCHK((k_heavy_z<M, NCXV>), dim3((unsigned)(nb - P.nb_tiled)), dim3(256), heavy_z_lds_bytes(NCXV, P.hv_max_batch_slots, deterministic), stream, d, hv, zz, cams.p, lambda, scale, hv_Z.p, Vinv.p, gp.p, jn2p.p, partial.p + npart, pivmm.p, (int)P.nb_tiled)
-                if (tile_ncx == 6) { DISPATCH_MODEL(L_HVZ, 6) } else if (tile_ncx == 14) { DISPATCH_MODEL(L_HVZ, 14) } else { DISPATCH_MODEL(L_HVZ, 15) }
-#undef L_HVZ
+                with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15>(tile_ncx, [&](auto NCX) {
+                    launch<k_heavy_z<M, NCX>>(dim3((unsigned)(nb - P.nb_tiled)), dim3(256), heavy_z_lds_bytes(NCX, P.hv_max_batch_slots, deterministic), d, hv, zz,
+                                              cams.p, lambda, scale, hv_Z.p, Vinv.p, gp.p, jn2p.p, partial.p + npart, pivmm.p, (int)P.nb_tiled);
+                }); });
                 npart += nb - P.nb_tiled;
             }
             if (ngiant > 0) {
-#define L_HVG(M, NCXV) LAUNCHK((k_heavy_z_giant<M, NCXV>), dim3((unsigned)ngiant), dim3(giant_threads), 0, stream, d, hv, zz, cams.p, lambda, scale, hv_Z.p, Vinv.p, gp.p, jn2p.p, partial.p + npart, pivmm.p)
-                if (tile_ncx == 6) { DISPATCH_MODEL(L_HVG, 6) } else if (tile_ncx == 14) { DISPATCH_MODEL(L_HVG, 14) } else { DISPATCH_MODEL(L_HVG, 15) }
-#undef L_HVG
+                with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15>(tile_ncx, [&](auto NCX) {
+                    launch<k_heavy_z_giant<M, NCX>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, hv, zz, cams.p, lambda, scale, hv_Z.p, Vinv.p, gp.p, jn2p.p,
+                                                    partial.p + npart, pivmm.p);
+                }); });
                 npart += ngiant;
             }
             mark(11);
-            LAUNCHK(k_heavy_syrk, dim3((unsigned)cdiv(hv.ntasks, 4)), dim3(256), 0, stream, d, hv, (const double *)hv_Z.p, S, g_red);
+            launch<k_heavy_syrk>(dim3((unsigned)cdiv(hv.ntasks, 4)), dim3(256), 0, d, hv, (const double *)hv_Z.p, S, g_red);
             mark(12);
         }
         if (no_tiles) mark(1);
         if (ngiant > 0 && !use_heavy) {               // points with more observations than a batch holds
-#define L_GIANT(M, IO) LAUNCHK((k_build_giant<M, IO>), dim3((unsigned)ngiant), dim3(giant_threads), 0, stream, d, zz, cams.p, lambda, scale, S, g_c, g_red, diagU, Vinv.p, gp.p, jn2p.p, partial.p + npart, pivmm.p)
-            if (P.with_io) { DISPATCH_MODEL(L_GIANT, true) } else { DISPATCH_MODEL(L_GIANT, false) }
-#undef L_GIANT
+            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
+                launch<k_build_giant<M, IO>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, zz, cams.p, lambda, scale, S, g_c, g_red, diagU, Vinv.p, gp.p, jn2p.p,
+                                             partial.p + npart, pivmm.p);
+            }); });
             npart += ngiant;
         }
-        if (deterministic && use_sig && !no_tiles) {
+        if (deterministic && route == TileRoute::sig && !no_tiles) {
             // deterministic mode: chunks whose turn at the tile never came (sig.hpp, spin cap) -- read with the scalars
             HIPCHK(hipMemcpyAsync(hpin + 60, gctr.p + 7, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
             det_timeout_pending = true;
@@ -915,7 +895,7 @@ struct Core {
         // red_scal[0] = the build kernels' residual sums + the prior rows' squares, red_scal[1] = owned
         // squared column norms of the point columns
         // (and keeps the copy of zz that the solve works from)
-        LAUNCHK(k_build_tail, dim3(grid_zs), dim3(1024), 0, stream, d, zz, partial.p, npart, jn2p.p, gpart.p, gctr.p + 2, red_scal,
+        launch<k_build_tail>(dim3(grid_zs), dim3(1024), 0, d, zz, partial.p, npart, jn2p.p, gpart.p, gctr.p + 2, red_scal,
                 zz != zlin.p ? zlin.p : (double *)nullptr);
     }
     // A linearisation at z that a damping loop has asked for but nobody has needed yet.  levenberg_marquardt.m
@@ -961,13 +941,13 @@ struct Core {
     void trace_only_pass(const double *zz) {
         stage(0);
         prep_cams(zz);
-#define L_TRACE(M, NCXV) LAUNCHK((k_trace_cm<M, NCXV>), dim3((unsigned)n_cm_chunks_all), dim3(256), 0, stream, d, zz, cams.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p, cm_chunk_cam.p, cm_chunk_start.p, partial.p)
         if (n_cm_chunks_all > 0) {
-            if (tile_ncx == 6) { DISPATCH_MODEL(L_TRACE, 6) } else if (tile_ncx == 14) { DISPATCH_MODEL(L_TRACE, 14) }
-            else if (tile_ncx == 15) { DISPATCH_MODEL(L_TRACE, 15) } else { DISPATCH_MODEL(L_TRACE, MAXCOL) }
+            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15, MAXCOL>(tile_ncx, [&](auto NCX) {
+                launch<k_trace_cm<M, NCX>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, d, zz, cams.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p,
+                                           cm_chunk_cam.p, cm_chunk_start.p, partial.p);
+            }); });
         }
-#undef L_TRACE
-        LAUNCHK(k_trace_tail, dim3(grid_zs), dim3(1024), 0, stream, d, gpart.p, gctr.p + 6, (const double *)partial.p, n_cm_chunks_all, hpin, ++mb_seq);
+        launch<k_trace_tail>(dim3(grid_zs), dim3(1024), 0, d, gpart.p, gctr.p + 6, (const double *)partial.p, n_cm_chunks_all, hpin, ++mb_seq);
         mb_armed = true; lin_pending = true;
         sync();
         pend_build = false;
@@ -998,20 +978,21 @@ struct Core {
     // sum of the envelope of S (incl. the right-hand-side row) over the ranks, after k_finish
     void allreduce_matrix() {
         if (!pk.p) pk.alloc((size_t)(pk_s_count + 3 * P.NS + 8));
-        LAUNCHK(k_pack_envelope, dim3((unsigned)P.NS), dim3(256), 0, stream, S, ldS, (int)P.NS, env_tail0, col_bend.p, col_off.p, pk.p, 1);
+        launch<k_pack_envelope>(dim3((unsigned)P.NS), dim3(256), 0, S, ldS, (int)P.NS, env_tail0, col_bend.p, col_off.p, pk.p, 1);
         do_allreduce(pk.p, pk_s_count);
-        LAUNCHK(k_pack_envelope, dim3((unsigned)P.NS), dim3(256), 0, stream, S, ldS, (int)P.NS, env_tail0, col_bend.p, col_off.p, pk.p, 0);
+        launch<k_pack_envelope>(dim3((unsigned)P.NS), dim3(256), 0, S, ldS, (int)P.NS, env_tail0, col_bend.p, col_off.p, pk.p, 0);
     }
     void finish_enqueue(const double *zz, double lambda, int scale) {
         // one rank, compact tiles: the factorisation's reset rides along (DfChol::reset_args)
         int *df_ctl = nullptr; unsigned long long *df_q = nullptr; int df_nq = 0;
         const bool ride = use_perm && !chol_in_place && !(mg_subtree && multi()) && dfchol.reset_args(df_ctl, df_q, df_nq);
-        LAUNCHK(k_finish, dim3((unsigned)cdiv(P.NS, 256)), dim3(256), 0, stream, d, zz, lambda, scale, S, g_c, g_red, diagU, jn2c.p, dscale.p,
+        launch<k_finish>(dim3((unsigned)cdiv(P.NS, 256)), dim3(256), 0, d, zz, lambda, scale, S, g_c, g_red, diagU, jn2c.p, dscale.p,
                 gpart.p, gctr.p + 3, (const double *)red_scal, scal.p, hpin, mg_subtree && multi() ? (const uint8_t *)z_mine.p : (const uint8_t *)nullptr,
                 ride ? info.p : (int *)nullptr, ride ? df_ctl : (int *)nullptr, ride ? df_q : (unsigned long long *)nullptr, ride ? df_nq : 0);
         if (ride) dfchol.reset_done = true;
         if (scale)      // D S D on the envelope
-            LAUNCHK(k_envelope_op, dim3((unsigned)P.NS), dim3(256), 0, stream, S, ldS, (int)P.NS, env_tail0, col_bend.p, (const double *)dscale.p);
+            launch<k_envelope_op>(dim3((unsigned)P.NS), dim3(256), 0, S, ldS, (int)P.NS, env_tail0, col_bend.p, (const double *)dscale.p, (double *)nullptr,
+                                  (unsigned long long *)nullptr);
     }
 
     // ---- K6: Cholesky of the reduced system; returns 0 or the failing pivot
@@ -1052,24 +1033,25 @@ struct Core {
         const int64_t n_sig_wg = sig_bs ? cdiv(sg_nchunks, 4) : 0;
         // (the slots of the tiled batches are not written then, and not summed: see k_sum_partials below)
         if (n_sig_wg > 0) {
-#define L_BACKS(M, NCXV) LAUNCHK((k_backsub_sig<M, NCXV>), dim3((unsigned)n_sig_wg), dim3(256), 0, stream, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p + 2 * (nb + ngiant), sg_chunk.p, (int)sg_nchunks, sg_gcam.p, sg_uv.p, P.uniform_w ? (const double *)nullptr : sg_w.p)
-            if (tile_ncx == 6) { DISPATCH_MODEL(L_BACKS, 6) } else { DISPATCH_MODEL(L_BACKS, 14) }
-#undef L_BACKS
+            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14>(tile_ncx, [&](auto NCX) {
+                launch<k_backsub_sig<M, NCX>>(dim3((unsigned)n_sig_wg), dim3(256), 0, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p + 2 * (nb + ngiant), sg_chunk.p,
+                                              (int)sg_nchunks, sg_gcam.p, sg_uv.p, P.uniform_w ? (const double *)nullptr : sg_w.p);
+            }); });
         }
         if (nb > b_first) {
-#define L_BACK(M, NCXV) LAUNCHK((k_backsub<M, NCXV>), dim3((unsigned)(nb - b_first)), dim3(P.BT), lds_back, stream, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p, (int)b_first)
-            if (tile_ncx == 6) { DISPATCH_MODEL(L_BACK, 6) } else if (tile_ncx == 14) { DISPATCH_MODEL(L_BACK, 14) } else if (tile_ncx == 15) { DISPATCH_MODEL(L_BACK, 15) } else { DISPATCH_MODEL(L_BACK, MAXCOL) }
-#undef L_BACK
+            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15, MAXCOL>(tile_ncx, [&](auto NCX) {
+                launch<k_backsub<M, NCX>>(dim3((unsigned)(nb - b_first)), dim3(P.BT), lds_back, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p, (int)b_first);
+            }); });
         }
         if (ngiant > 0) {
-#define L_BACKG(M, IO) LAUNCHK((k_backsub_giant<M, IO>), dim3((unsigned)ngiant), dim3(giant_threads), 0, stream, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p + 2 * nb)
-            if (P.with_io) { DISPATCH_MODEL(L_BACKG, true) } else { DISPATCH_MODEL(L_BACKG, false) }
-#undef L_BACKG
+            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
+                launch<k_backsub_giant<M, IO>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p + 2 * nb);
+            }); });
         }
         mark(5);
         // one launch: the sums of the back-substitution kernels, the prior rows' share, g'p, p'p, the pivot
         // extremes of the reduced system; on one rank straight into the pinned mailbox
-        LAUNCHK(k_prior_jv, dim3(grid_zs), dim3(1024), 0, stream, d, zlin.p, dz.p, g_c, gp.p, gpart.p, gctr.p + 4,
+        launch<k_prior_jv>(dim3(grid_zs), dim3(1024), 0, d, zlin.p, dz.p, g_c, gp.p, gpart.p, gctr.p + 4,
                 (const double *)(partial.p + 2 * b_first), nb - b_first + ngiant + n_sig_wg, (const double *)ldiag.p, pivmm.p,
                 (const int *)info.p, scal.p, multi() ? (double *)nullptr : hpin, ++mb_seq,
                 mg_subtree && multi() ? (const uint8_t *)piv_have.p : (const uint8_t *)nullptr);
@@ -1184,22 +1166,15 @@ struct Core {
         if (hCIO && P.nIOu > 0) dCIO.alloc((size_t)P.nIOu * P.nIOu);
         if (hCEO || (hCIO && P.nIOu > 0)) {
             const int64_t tot = 36 * (int64_t)P.nc + (int64_t)P.nIOu * P.nIOu;
-            LAUNCHK(k_cov_cam, dim3((unsigned)cdiv(tot, 256)), dim3(256), 0, stream, d, SV, s02, dCEO.p, dCIO.p);
+            launch<k_cov_cam>(dim3((unsigned)cdiv(tot, 256)), dim3(256), 0, d, SV, s02, dCEO.p, dCIO.p);
         }
         if (hCOP) {
             dCOP.alloc((size_t)9 * P.np);
             HIPCHK(hipMemsetAsync(dCOP.p, 0, (size_t)9 * P.np * sizeof(double), stream));
-            const size_t lds_cov = ((size_t)P.BT * P.ncolmax * 3 + (size_t)P.BT * 6) * sizeof(double);
-            if (nb > 0) {
-#define L_COV(M, IO) LAUNCHK((k_cov_points<M, IO>), dim3((unsigned)nb), dim3(P.BT), lds_cov, stream, d, z.p, cams.p, Vinv.p, SV, s02, dCOP.p)
-                if (P.with_io) { DISPATCH_MODEL(L_COV, true) } else { DISPATCH_MODEL(L_COV, false) }
-#undef L_COV
-            }
-            if (ngiant > 0) {
-#define L_COVG(M, IO) LAUNCHK((k_cov_giant<M, IO>), dim3((unsigned)ngiant), dim3(giant_threads), 0, stream, d, z.p, cams.p, Vinv.p, SV, s02, dCOP.p)
-                if (P.with_io) { DISPATCH_MODEL(L_COVG, true) } else { DISPATCH_MODEL(L_COVG, false) }
-#undef L_COVG
-            }
+            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
+                if (nb > 0) launch<k_cov_points<M, IO>>(dim3((unsigned)nb), dim3(P.BT), lds_cov, d, z.p, cams.p, Vinv.p, SV, s02, dCOP.p, HatOut{});
+                if (ngiant > 0) launch<k_cov_giant<M, IO>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, z.p, cams.p, Vinv.p, SV, s02, dCOP.p, HatOut{});
+            }); });
             if (multi()) do_allreduce(dCOP.p, (int64_t)9 * P.np);   // blocks of the other shards' points
             cop_tmp.resize((size_t)9 * P.np);
             HIPCHK(hipMemcpyAsync(cop_tmp.data(), dCOP.p, (size_t)9 * P.np * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1227,24 +1202,17 @@ struct Core {
         HIPCHK(hipMemsetAsync(qvv.p, 0, (size_t)3 * P.no * sizeof(double), stream));
         HIPCHK(hipMemsetAsync(dCz.p, 0, (size_t)P.NZ * sizeof(double), stream));
         const int64_t nCcc = (int64_t)P.nc * P.ncolmax * P.ncolmax;
-        if (nCcc > 0) LAUNCHK(k_hat_cam_blocks, dim3((unsigned)cdiv(nCcc, 256)), dim3(256), 0, stream, d, cams.p, SV, Ccc.p);
+        if (nCcc > 0) launch<k_hat_cam_blocks>(dim3((unsigned)cdiv(nCcc, 256)), dim3(256), 0, d, cams.p, SV, Ccc.p);
         HatOut hat;
         hat.Ccc = Ccc.p; hat.qvv = qvv.p; hat.dCz = dCz.p;
         if (ngiant > 0) {
             gscr.alloc((size_t)(P.giant_start.back() - P.giant_start.front()) * 9);
             hat.gscr = gscr.p;
         }
-        const size_t lds_cov = ((size_t)P.BT * P.ncolmax * 3 + (size_t)P.BT * 6) * sizeof(double);
-        if (nb > 0) {
-#define L_HAT(M, IO) LAUNCHK((k_cov_points<M, IO, true>), dim3((unsigned)nb), dim3(P.BT), lds_cov, stream, d, z.p, cams.p, Vinv.p, SV, 1.0, (double *)nullptr, hat)
-            if (P.with_io) { DISPATCH_MODEL(L_HAT, true) } else { DISPATCH_MODEL(L_HAT, false) }
-#undef L_HAT
-        }
-        if (ngiant > 0) {
-#define L_HATG(M, IO) LAUNCHK((k_cov_giant<M, IO, true>), dim3((unsigned)ngiant), dim3(giant_threads), 0, stream, d, z.p, cams.p, Vinv.p, SV, 1.0, (double *)nullptr, hat)
-            if (P.with_io) { DISPATCH_MODEL(L_HATG, true) } else { DISPATCH_MODEL(L_HATG, false) }
-#undef L_HATG
-        }
+        with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
+            if (nb > 0) launch<k_cov_points<M, IO, true>>(dim3((unsigned)nb), dim3(P.BT), lds_cov, d, z.p, cams.p, Vinv.p, SV, 1.0, (double *)nullptr, hat);
+            if (ngiant > 0) launch<k_cov_giant<M, IO, true>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, z.p, cams.p, Vinv.p, SV, 1.0, (double *)nullptr, hat);
+        }); });
         if (multi()) {                               // the other shards' observations and points
             do_allreduce(qvv.p, 3 * P.no);
             do_allreduce(dCz.p + P.NS, P.NZ - P.NS);
@@ -1253,7 +1221,7 @@ struct Core {
             rp.alloc((size_t)nprior);
             pz.alloc((size_t)nprior);
             HIPCHK(hipMemcpyAsync(pz.p, P.prior_z.data(), (size_t)nprior * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-            LAUNCHK(k_hat_prior, dim3((unsigned)cdiv(nprior, 256)), dim3(256), 0, stream, d, SV, pz.p, nprior, dCz.p, rp.p);
+            launch<k_hat_prior>(dim3((unsigned)cdiv(nprior, 256)), dim3(256), 0, d, SV, pz.p, nprior, dCz.p, rp.p);
             HIPCHK(hipMemcpyAsync(hrp, rp.p, (size_t)nprior * sizeof(double), hipMemcpyDeviceToHost, stream));
         }
         HIPCHK(hipMemcpyAsync(hqvv, qvv.p, (size_t)3 * P.no * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1262,32 +1230,36 @@ struct Core {
     // ||J v||^2 and r'Jv at the linearisation point, ||v||^2 over owned entries
     void jtimes(const double *v, double &JvJv, double &rJv, double &vv) {
         if (!cams_at_lin) { prep_cams(zlin.p); cams_at_lin = true; }
-#define L_JT(M, NCXV) LAUNCHK((k_jtimes<M, NCXV>), dim3(grid_obs), dim3(256), 0, stream, d, zlin.p, cams.p, v, partial.p)
-        if (tile_ncx == 6) { DISPATCH_MODEL(L_JT, 6) } else if (tile_ncx == 14) { DISPATCH_MODEL(L_JT, 14) } else if (tile_ncx == 15) { DISPATCH_MODEL(L_JT, 15) } else { DISPATCH_MODEL(L_JT, MAXCOL) }
-#undef L_JT
-        LAUNCHK(k_prior_jv, dim3(grid_zs), dim3(1024), 0, stream, d, zlin.p, v, g_c, gp.p, gpart.p, gctr.p + 4,
-                (const double *)partial.p, (int64_t)grid_obs, (const double *)nullptr, pivmm.p, (const int *)info.p, scal.p, (double *)nullptr, 0ull);
+        with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15, MAXCOL>(tile_ncx, [&](auto NCX) {
+            launch<k_jtimes<M, NCX>>(dim3(grid_obs), dim3(256), 0, d, zlin.p, cams.p, v, partial.p);
+        }); });
+        launch<k_prior_jv>(dim3(grid_zs), dim3(1024), 0, d, zlin.p, v, g_c, gp.p, gpart.p, gctr.p + 4,
+                (const double *)partial.p, (int64_t)grid_obs, (const double *)nullptr, pivmm.p, (const int *)info.p, scal.p, (double *)nullptr, 0ull, (const uint8_t *)nullptr);
         do_allreduce(scal.p, 8);
         double h[8];
         read_scal(h, 8);
         JvJv = h[0] + h[4]; rJv = h[1] + h[5]; vv = h[6];
     }
     double dot_owned(const double *a, const double *b) {
-        LAUNCHK(k_dot, dim3(grid_z), dim3(256), 0, stream, P.NZ, z_mine.p, a, b, partial.p);
-        LAUNCHK((k_sum_partials<1>), dim3(1), dim3(1024), 0, stream, partial.p, (int64_t)grid_z, scal.p, 0);
+        launch<k_dot>(dim3(grid_z), dim3(256), 0, P.NZ, z_mine.p, a, b, partial.p);
+        launch<k_sum_partials<1>>(dim3(1), dim3(1024), 0, partial.p, (int64_t)grid_z, scal.p, 0);
         do_allreduce(scal.p, 1);
         double s;
         read_scal(&s, 1);
         return s;
     }
     void axpby(double a, const double *x, double b, const double *y2, double *y) {
-        LAUNCHK(k_axpby, dim3((unsigned)cdiv(P.NZ, 256)), dim3(256), 0, stream, P.NZ, a, x, b, y2, y);
+        launch<k_axpby>(dim3((unsigned)cdiv(P.NZ, 256)), dim3(256), 0, P.NZ, a, x, b, y2, y);
     }
     void gradient(double *g) {
-        LAUNCHK(k_gradient, dim3((unsigned)cdiv(P.NZ, 256)), dim3(256), 0, stream, d, g_c, gp.p, g);
+        launch<k_gradient>(dim3((unsigned)cdiv(P.NZ, 256)), dim3(256), 0, d, g_c, gp.p, g);
     }
     void colnorm2(double *out) {
-        LAUNCHK(k_jn2, dim3((unsigned)cdiv(P.NZ, 256)), dim3(256), 0, stream, d, jn2c.p, jn2p.p, out);
+        launch<k_jn2>(dim3((unsigned)cdiv(P.NZ, 256)), dim3(256), 0, d, jn2c.p, jn2p.p, out);
+    }
+    // Jacobian blocks of every observation at zz (the camera records in cams)
+    void jac_blocks(const double *zz, double *a, double *b, double *cc) {
+        with_value<2, 3, 4, 5>(P.model, [&](auto M) { launch<k_jac_blocks<M>>(dim3((unsigned)cdiv(nobs, 256)), dim3(256), 0, d, zz, cams.p, a, b, cc); });
     }
     void copy(double *dst, const double *src) { HIPCHK(hipMemcpyAsync(dst, src, P.NZ * 8, hipMemcpyDeviceToDevice, stream)); }
     void accept_trial() { std::swap(z.p, zt.p); }    // z <- the trial point: the buffers change roles (nothing keeps their addresses)
@@ -1798,7 +1770,7 @@ static void export_residuals(Core &c, const double *zdev, double *r_unw, double 
         tmpw.alloc(2 * std::max<int64_t>(P.no, 1));
         HIPCHK(hipMemsetAsync(tmpw.p, 0, 2 * P.no * 8, c.stream));
         if (c.nobs > 0)
-            LAUNCHK(k_weight_rows, dim3((unsigned)cdiv(c.nobs, 256)), dim3(256), 0, c.stream, c.d, dev_unw, tmpw.p);
+            c.launch<k_weight_rows>(dim3((unsigned)cdiv(c.nobs, 256)), dim3(256), 0, c.d, dev_unw, tmpw.p);
     }
     if (c.multi()) {
         c.do_allreduce(dev_unw, 2 * P.no);
@@ -1844,11 +1816,7 @@ int dbat_hip_jacobian_blocks(dbat_hip_handle *h, const double *x, double *JEO, d
     if (JEO) { a.alloc(12 * no); HIPCHK(hipMemsetAsync(a.p, 0, 12 * no * 8, c.stream)); }
     if (JOP) { b.alloc(6 * no); HIPCHK(hipMemsetAsync(b.p, 0, 6 * no * 8, c.stream)); }
     if (JIO) { cc.alloc(2 * (int64_t)P.nIOrows * no); HIPCHK(hipMemsetAsync(cc.p, 0, 2 * (int64_t)P.nIOrows * no * 8, c.stream)); }
-    if (c.nobs > 0) {
-#define L_JB(M, dummy) LAUNCHK((k_jac_blocks<M>), dim3((unsigned)cdiv(c.nobs, 256)), dim3(256), 0, c.stream, c.d, c.zt.p, c.cams.p, a.p, b.p, cc.p)
-        switch (P.model) { case 2: L_JB(2, 0); break; case 3: L_JB(3, 0); break; case 4: L_JB(4, 0); break; default: L_JB(5, 0); break; }
-#undef L_JB
-    }
+    if (c.nobs > 0) c.jac_blocks(c.zt.p, a.p, b.p, cc.p);
     if (JEO) HIPCHK(hipMemcpyAsync(JEO, a.p, 12 * P.no * 8, hipMemcpyDeviceToHost, c.stream));
     if (JOP) HIPCHK(hipMemcpyAsync(JOP, b.p, 6 * P.no * 8, hipMemcpyDeviceToHost, c.stream));
     if (JIO) HIPCHK(hipMemcpyAsync(JIO, cc.p, 2 * (int64_t)P.nIOrows * P.no * 8, hipMemcpyDeviceToHost, c.stream));
@@ -1891,9 +1859,9 @@ int dbat_hip_jacobian_sample(dbat_hip_handle *h, const double *x, int64_t n, con
     const int R = P.nIOrows;
     DevBuf<double> dr, a, b, cc;
     dr.alloc(2 * n); a.alloc(12 * n); b.alloc(6 * n); cc.alloc(2 * (int64_t)R * n);
-#define L_JS(M, dummy) LAUNCHK((k_jac_sample<M>), dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c.stream, c.d, c.zt.p, c.cams.p, n, dpos.p, dr.p, a.p, b.p, cc.p)
-    switch (P.model) { case 2: L_JS(2, 0); break; case 3: L_JS(3, 0); break; case 4: L_JS(4, 0); break; default: L_JS(5, 0); break; }
-#undef L_JS
+    with_value<2, 3, 4, 5>(P.model, [&](auto M) {
+        c.launch<k_jac_sample<M>>(dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c.d, c.zt.p, c.cams.p, n, dpos.p, dr.p, a.p, b.p, cc.p);
+    });
     HIPCHK(hipMemcpyAsync(res, dr.p, 2 * n * 8, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipMemcpyAsync(JEO, a.p, 12 * n * 8, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipMemcpyAsync(JOP, b.p, 6 * n * 8, hipMemcpyDeviceToHost, c.stream));
@@ -1942,11 +1910,7 @@ int dbat_hip_jacobian_csc(dbat_hip_handle *h, const double *x, int32_t weighted,
     const int64_t no = std::max<int64_t>(P.no, 1);
     DevBuf<double> a, b, cc;
     a.alloc(12 * no); b.alloc(6 * no); cc.alloc(2 * (int64_t)R * no);
-    if (c.nobs > 0) {
-#define L_JB(M, dummy) LAUNCHK((k_jac_blocks<M>), dim3((unsigned)cdiv(c.nobs, 256)), dim3(256), 0, c.stream, c.d, c.zt.p, c.cams.p, a.p, b.p, cc.p)
-        switch (P.model) { case 2: L_JB(2, 0); break; case 3: L_JB(3, 0); break; case 4: L_JB(4, 0); break; default: L_JB(5, 0); break; }
-#undef L_JB
-    }
+    if (c.nobs > 0) c.jac_blocks(c.zt.p, a.p, b.p, cc.p);
     std::vector<double> JEO((size_t)12 * no), JOP((size_t)6 * no), JIO((size_t)2 * R * no);
     HIPCHK(hipMemcpyAsync(JEO.data(), a.p, JEO.size() * 8, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipMemcpyAsync(JOP.data(), b.p, JOP.size() * 8, hipMemcpyDeviceToHost, c.stream));
@@ -2036,7 +2000,7 @@ int dbat_hip_jtimes_sqnorm(dbat_hip_handle *h, const double *v, double *sqnorm) 
     HIPCHK(hipMemsetAsync(c.vtmp.p, 0, c.P.NZ * 8, c.stream));
     if (c.P.n) {
         HIPCHK(hipMemcpyAsync(c.xbuf.p, v, c.P.n * 8, hipMemcpyHostToDevice, c.stream));
-        LAUNCHK(k_scatter_x, dim3((unsigned)cdiv(c.P.n, 256)), dim3(256), 0, c.stream, c.P.n, c.x2z.p, c.xbuf.p, c.vtmp.p);
+        c.launch<k_scatter_x>(dim3((unsigned)cdiv(c.P.n, 256)), dim3(256), 0, c.P.n, c.x2z.p, c.xbuf.p, c.vtmp.p);
     }
     double a, b, vv;
     c.jtimes(c.vtmp.p, a, b, vv);
@@ -2054,9 +2018,9 @@ static void jtimes_rows(Core &c, const double *v_dev, double *Jv) {
     DevBuf<double> out;
     out.alloc(2 * std::max<int64_t>(P.no, 1));
     if (c.nobs > 0) {
-#define L_JTV(M, NCXV) LAUNCHK((k_jtimes_vec<M, NCXV>), dim3((unsigned)cdiv(c.nobs, 256)), dim3(256), 0, c.stream, c.d, c.zlin.p, c.cams.p, v_dev, out.p)
-        if (c.tile_ncx == 6) { DISPATCH_MODEL(L_JTV, 6) } else if (c.tile_ncx == 14) { DISPATCH_MODEL(L_JTV, 14) } else if (c.tile_ncx == 15) { DISPATCH_MODEL(L_JTV, 15) } else { DISPATCH_MODEL(L_JTV, MAXCOL) }
-#undef L_JTV
+        with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15, MAXCOL>(c.tile_ncx, [&](auto NCX) {
+            c.launch<k_jtimes_vec<M, NCX>>(dim3((unsigned)cdiv(c.nobs, 256)), dim3(256), 0, c.d, c.zlin.p, c.cams.p, v_dev, out.p);
+        }); });
     }
     std::vector<double> vz(P.NZ);
     HIPCHK(hipMemcpyAsync(Jv, out.p, 2 * P.no * 8, hipMemcpyDeviceToHost, c.stream));
@@ -2078,7 +2042,7 @@ int dbat_hip_jtimes(dbat_hip_handle *h, const double *v, double *Jv) {
     HIPCHK(hipMemsetAsync(c.vtmp.p, 0, P.NZ * 8, c.stream));
     if (P.n) {
         HIPCHK(hipMemcpyAsync(c.xbuf.p, v, P.n * 8, hipMemcpyHostToDevice, c.stream));
-        LAUNCHK(k_scatter_x, dim3((unsigned)cdiv(P.n, 256)), dim3(256), 0, c.stream, P.n, c.x2z.p, c.xbuf.p, c.vtmp.p);
+        c.launch<k_scatter_x>(dim3((unsigned)cdiv(P.n, 256)), dim3(256), 0, P.n, c.x2z.p, c.xbuf.p, c.vtmp.p);
     }
     jtimes_rows(c, c.vtmp.p, Jv);
     return DBAT_HIP_OK;
@@ -2312,8 +2276,8 @@ int dbat_hip_forwintersect(dbat_hip_handle *h, const double *x, const uint8_t *s
     DevBuf<double> dOP;
     dOP.alloc((size_t)3 * std::max(P.np, 1));
     HIPCHK(hipMemsetAsync(dOP.p, 0, (size_t)3 * P.np * sizeof(double), c.stream));
-    if (c.nb > 0) LAUNCHK(k_forwintersect, dim3((unsigned)c.nb), dim3(P.BT), (size_t)P.BT * 9 * sizeof(double), c.stream, c.d, c.cams.p, dOP.p);
-    if (c.ngiant > 0) LAUNCHK(k_forwintersect_giant, dim3((unsigned)c.ngiant), dim3(256), 0, c.stream, c.d, c.cams.p, dOP.p);
+    if (c.nb > 0) c.launch<k_forwintersect>(dim3((unsigned)c.nb), dim3(P.BT), (size_t)P.BT * 9 * sizeof(double), c.d, c.cams.p, dOP.p);
+    if (c.ngiant > 0) c.launch<k_forwintersect_giant>(dim3((unsigned)c.ngiant), dim3(256), 0, c.d, c.cams.p, dOP.p);
     if (c.multi()) c.do_allreduce(dOP.p, (int64_t)3 * P.np);             // every point is computed by its owner
     std::vector<double> tmp((size_t)3 * P.np);
     HIPCHK(hipMemcpyAsync(tmp.data(), dOP.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, c.stream));
@@ -2356,7 +2320,7 @@ int dbat_hip_resect(int32_t device, int32_t n_images, const int64_t *pt_start, c
     dX.upload(std::vector<double>(X, X + 3 * npt)); dx.upload(std::vector<double>(xn, xn + 2 * npt));
     dtri.upload(std::vector<int32_t>(tri, tri + 3 * ntri));
     dP.alloc((size_t)12 * n_images); dr.alloc((size_t)n_images);
-    LAUNCHK(k_resect, dim3((unsigned)n_images), dim3(64), 0, (hipStream_t)nullptr, n_images, dps.p, dX.p, dx.p, dts.p, dtri.p, 1, dP.p, dr.p);
+    launch<k_resect>(dim3((unsigned)n_images), dim3(64), 0, (hipStream_t)nullptr, n_images, dps.p, dX.p, dx.p, dts.p, dtri.p, 1, dP.p, dr.p);
     HIPCHK(hipMemcpy(P, dP.p, (size_t)12 * n_images * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(rms, dr.p, (size_t)n_images * sizeof(double), hipMemcpyDeviceToHost));
     return DBAT_HIP_OK;
@@ -2374,13 +2338,9 @@ int dbat_hip_chol_stats(const dbat_hip_handle *h, int64_t *st) {
 int dbat_hip_build_kernel_name(const dbat_hip_handle *h, char *buf, int32_t buf_len) {
     if (!h || !buf || buf_len < 2) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
     const Core &c = *h->core;
-    const char *nm = c.use_heavy ? "k_heavy_z + k_heavy_syrk" : "k_build";      // (nothing tiled: the kernels of the untiled points)
-    if (c.ntiles > 0 && c.P.nb_tiled > 0) {
-        if (c.use_sig) nm = "k_build_sig";
-        else if (c.use_tile3 && c.tile_ncx == 6) nm = "k_build_tile3";
-        else if (c.use_tile2 && c.tile_ncx <= 15) nm = "k_build_tile2";
-        else nm = "k_build";
-    }
+    using R = Core::TileRoute;
+    const char *nm = c.route == R::sig ? "k_build_sig" : c.route == R::tile3 ? "k_build_tile3" : c.route == R::tile2 ? "k_build_tile2"
+                   : c.use_heavy ? "k_heavy_z + k_heavy_syrk" : "k_build";      // (nothing tiled: the kernels of the untiled points)
     snprintf(buf, (size_t)buf_len, "%s", nm);
     return DBAT_HIP_OK;
 }

@@ -2871,12 +2871,6 @@ __global__ void k_weight_rows(DevProblem d, const double *__restrict__ r_unw, do
     r_wgt[2 * row + 1] = r_unw[2 * row + 1] * w1;
 }
 
-__global__ void k_unscale(int64_t NS, const double *__restrict__ q, const double *__restrict__ ds,
-                          double *__restrict__ dz) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < NS) dz[i] = ds[i] * q[i];
-}
-
 // ---------------------------------------------------------------- K7 ----
 // Back-substitution dp = -V^-1 (g_p + W' dc) and the sums ||Jp||^2, r'Jp over
 // the image rows.  dz[0..NS) holds dc on entry; dz[NS..) receives dp.
