@@ -104,6 +104,25 @@ class Result(C.Structure):
     ]
 
 
+LOSS = {'huber': 0, 'cauchy': 1}
+SCALE = {'apriori': 0, 'mad': 1}
+ROBUST_MAX_OUTER = 64          # DBAT_HIP_ROBUST_MAX_OUTER
+
+
+class RobustOptions(C.Structure):
+    _fields_ = [
+        ('loss', C.c_int32), ('k', C.c_double), ('scale', C.c_int32), ('max_outer', C.c_int32),
+        ('weight_tol', C.c_double),
+    ]
+
+
+class RobustResult(C.Structure):
+    _fields_ = [
+        ('outer', C.c_int32), ('converged', C.c_int32), ('inner_iters', C.c_int32 * ROBUST_MAX_OUTER),
+        ('scale', C.c_double * ROBUST_MAX_OUTER), ('max_change', C.c_double), ('reweight_s', C.c_double),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 
 # every symbol include/dbat_hip.h declares: name -> (restype, argtypes)
@@ -154,6 +173,11 @@ SYMBOLS = {
     'dbat_hip_chol_stats': (C.c_int, [_H, C.POINTER(C.c_int64)]),
     'dbat_hip_posterior_cov': (C.c_int, [_H, _dp, C.c_double, _dp, _dp, _dp, _dp]),
     'dbat_hip_redundancy': (C.c_int, [_H, _dp, _dp, _dp]),
+    'dbat_hip_default_robust_options': (C.c_int, [C.c_int32, C.POINTER(RobustOptions)]),
+    'dbat_hip_robust_weights': (C.c_int, [_H, _dp, C.POINTER(RobustOptions), _dp, _dp, _dp]),
+    'dbat_hip_set_obs_weights': (C.c_int, [_H, _dp]),
+    'dbat_hip_solve_robust': (C.c_int, [_H, C.POINTER(Options), C.POINTER(RobustOptions), _dp, C.POINTER(Result),
+                                        _dp, _dp, _dp, _dp, C.POINTER(RobustResult), _dp]),
 }
 DEBUG_SYMBOLS = {
     'dbat_hip_debug_plan_digest': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_uint64), C.c_int32, C.c_char_p, C.c_int32]),
@@ -579,6 +603,43 @@ class Handle:
         check(self.lib.dbat_hip_redundancy(self.h, dptr(x), dptr(qvv), dptr(rp)))
         return qvv[:3 * no].reshape(3, no, order='F'), rp[:self.m - 2 * no]
 
+    def robust_weights(self, x, ropt):
+        """One reweighting evaluation at x, not applied (dbat_hip_robust_weights): (omega, s_norm, scale), the two
+        vectors per IP column."""
+        x = np.ascontiguousarray(x, float)
+        no = int(self.prob.n_obs)
+        om, sn, sc = np.zeros(max(no, 1)), np.zeros(max(no, 1)), C.c_double()
+        check(self.lib.dbat_hip_robust_weights(self.h, dptr(x), C.byref(ropt), dptr(om), dptr(sn), C.byref(sc)))
+        return om[:no], sn[:no], sc.value
+
+    def set_obs_weights(self, omega):
+        """Weight factors omega in (0, 1] per IP column (dbat_hip_set_obs_weights); None: back to the base weights."""
+        if omega is None:
+            check(self.lib.dbat_hip_set_obs_weights(self.h, None))
+            return
+        om = np.ascontiguousarray(omega, float).ravel()
+        if om.size != int(self.prob.n_obs):
+            raise ValueError('set_obs_weights: %d values for %d image points' % (om.size, int(self.prob.n_obs)))
+        check(self.lib.dbat_hip_set_obs_weights(self.h, dptr(om)))
+
+    def solve_robust(self, x0, opt, ropt):
+        """The IRLS outer loop (dbat_hip_solve_robust): (x, Result, res, damp, aux, T, RobustResult, omega) -- the
+        arrays of the last inner solve, as solve() returns them, and the weight factors per IP column."""
+        x = np.ascontiguousarray(x0, float).copy()
+        res, rr = Result(), RobustResult()
+        mi = opt.max_iter
+        r = np.full(mi + 3, np.nan)
+        damp = np.full(2 * mi + 4, np.nan)
+        aux = np.full(2 * mi + 4, np.nan)
+        trace = np.empty(self.n * (mi + 2)) if opt.store_trace else None
+        no = int(self.prob.n_obs)
+        om = np.ones(max(no, 1))
+        check(self.lib.dbat_hip_solve_robust(self.h, C.byref(opt), C.byref(ropt), dptr(x), C.byref(res), dptr(r),
+                                             dptr(damp), dptr(aux), dptr(trace), C.byref(rr), dptr(om)))
+        T = (trace[:self.n * res.n_trace].reshape(self.n, res.n_trace, order='F')
+             if trace is not None else None)
+        return x, res, r[:res.n_res], damp[:res.n_damp], aux, T, rr, om[:no]
+
     def set_x(self, x):
         x = np.ascontiguousarray(x, float)
         check(self.lib.dbat_hip_set_x(self.h, dptr(x)))
@@ -668,6 +729,18 @@ def clear_cache():
 def default_options(damping='gna'):
     o = Options()
     check(load().dbat_hip_default_options(DAMP[damping.lower()], C.byref(o)))
+    return o
+
+
+def robust_options(loss, k=None, scale='apriori', max_outer=10, weight_tol=1e-3):
+    """dbat_hip_robust_options for loss 'huber' | 'cauchy' (k None: the library's default for the loss)."""
+    o = RobustOptions()
+    check(load().dbat_hip_default_robust_options(LOSS[loss], C.byref(o)))
+    if k is not None:
+        o.k = float(k)
+    o.scale = SCALE[scale]
+    o.max_outer = int(max_outer)
+    o.weight_tol = float(weight_tol)
     return o
 
 

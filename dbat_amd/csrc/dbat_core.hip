@@ -24,6 +24,7 @@
 #include "heavy.hpp"
 #include "plan.hpp"
 #include "resect.hpp"
+#include "robust.hpp"
 
 namespace dbat {
 
@@ -284,6 +285,7 @@ struct Core {
         d.io_src = io_src.p; d.io_fixed = io_fixed.p; d.px = px.p; d.cam_w = cam_w.p;
         d.z_est = z_est.p; d.z_mine = z_mine.p; d.z_prw = z_prw.p; d.z_prv = z_prv.p;
         d.o_cam = o_cam.p; d.o_pt = o_pt.p; d.o_uv = o_uv.p; d.o_w = P.uniform_w ? nullptr : o_w.p;
+        pw = !P.uniform_w;
         d.o_seg = o_seg.p; d.o_row = o_row.p; d.batch_start = batch_start.p;
         d.CMAX = P.CMAX; d.ablate = env_int("DBAT_HIP_ABLATE", 0); d.trace_only = 0;
         d.any_prior = 0;
@@ -435,6 +437,7 @@ struct Core {
     // dbat_hip_set_values: new parameter values / prior observations for the same structure.  The host plan has them
     // already (plan_set_values); here the device copies, and everything a previous solve left behind is forgotten.
     void set_values(bool io_changed) {
+        robust_reset();
         HIPCHK(hipMemcpyAsync(z.p, P.z0.data(), P.NZ * 8, hipMemcpyHostToDevice, stream));
         HIPCHK(hipMemcpyAsync(io_fixed.p, P.io_fixed.data(), P.io_fixed.size() * 8, hipMemcpyHostToDevice, stream));
         if (d.any_prior) {
@@ -678,7 +681,7 @@ struct Core {
         with_value<2, 3, 4, 5>(P.model, [&](auto M) {
             with_value<false, true>(uv_pre, [&](auto PRE) {
                 if (n_cm_chunks_all > 0)
-                    launch<k_residual_cm<M, PRE>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, d, zz, cams_f.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p,
+                    launch<k_residual_cm<M, PRE>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, d, zz, cams_f.p, cm_pt.p, cm_uv.p, pw ? cm_w.p : (const double *)nullptr,
                                                   cm_chunk_cam.p, cm_chunk_start.p, partial.p, res_tail ? gctr.p + 1 : (unsigned *)nullptr, scal.p, hpin, res_tail ? ++mb_seq : 0ull);
                 mark(7);
                 if (r_w_out || r_unw_out) launch<k_residual<M, PRE>>(dim3(grid_obs), dim3(256), 0, d, zz, cams_f.p, rpart.p, r_w_out, r_unw_out);
@@ -749,7 +752,7 @@ struct Core {
 
     // camera side J_c'J_c, J_c'r and squared column norms of the camera-major chunks [q0, q0 + nq)
     void cam_normal(const double *zz, int64_t q0, int64_t nq, int ncx) {
-        const double *w = P.uniform_w ? (const double *)nullptr : cm_w.p;
+        const double *w = pw ? cm_w.p : (const double *)nullptr;
         with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15>(ncx, [&](auto NCX) {
             if constexpr (NCX == 6)
                 launch<k_cam_normal6<M>>(dim3((unsigned)nq), dim3(256), 0, d, zz, cams.p, cm_pt.p, cm_uv.p, w, cm_chunk_cam.p + q0, cm_chunk_start.p + q0, S, g_c, g_red, diagU);
@@ -796,7 +799,7 @@ struct Core {
             mark(0);                                 // events around the tile kernel alone (bench roofline)
             with_value<2, 3, 4, 5>(P.model, [&](auto M) {
                 if (route == TileRoute::sig) {
-                    with_value<6, 14>(tile_ncx, [&](auto NCX) { with_value<4, 5>(sig_rb, [&](auto RB) { with_value<false, true>(!P.uniform_w, [&](auto PW) {
+                    with_value<6, 14>(tile_ncx, [&](auto NCX) { with_value<4, 5>(sig_rb, [&](auto RB) { with_value<false, true>(pw, [&](auto PW) {
                         launch<k_build_sig<M, RB, NCX, PW>>(dim3((unsigned)std::min<int64_t>(ntiles, n_cu)), dim3(64 * sig_waves(RB, NCX > 6)), sig_lds_bytes(RB, NCX > 6),
                                                             d, zz, cams.p, lambda, scale, S, g_red, Vinv.p, gp.p, jn2p.p, partial.p, pivmm.p, sg_chunk.p, sg_tile_chunk0.p,
                                                             sg_lc.p, sg_uv.p, PW ? sg_w.p : (const double *)nullptr, gctr.p + 5);
@@ -943,7 +946,7 @@ struct Core {
         prep_cams(zz);
         if (n_cm_chunks_all > 0) {
             with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15, MAXCOL>(tile_ncx, [&](auto NCX) {
-                launch<k_trace_cm<M, NCX>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, d, zz, cams.p, cm_pt.p, cm_uv.p, P.uniform_w ? (const double *)nullptr : cm_w.p,
+                launch<k_trace_cm<M, NCX>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, d, zz, cams.p, cm_pt.p, cm_uv.p, pw ? cm_w.p : (const double *)nullptr,
                                            cm_chunk_cam.p, cm_chunk_start.p, partial.p);
             }); });
         }
@@ -1035,7 +1038,7 @@ struct Core {
         if (n_sig_wg > 0) {
             with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14>(tile_ncx, [&](auto NCX) {
                 launch<k_backsub_sig<M, NCX>>(dim3((unsigned)n_sig_wg), dim3(256), 0, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p + 2 * (nb + ngiant), sg_chunk.p,
-                                              (int)sg_nchunks, sg_gcam.p, sg_uv.p, P.uniform_w ? (const double *)nullptr : sg_w.p);
+                                              (int)sg_nchunks, sg_gcam.p, sg_uv.p, pw ? sg_w.p : (const double *)nullptr);
             }); });
         }
         if (nb > b_first) {
@@ -1226,6 +1229,171 @@ struct Core {
         }
         HIPCHK(hipMemcpyAsync(hqvv, qvv.p, (size_t)3 * P.no * sizeof(double), hipMemcpyDeviceToHost, stream));
         sync();
+    }
+    // ---- robust reweighting (robust.hpp).  A handle that never sees a robust call has none of this: pw follows the
+    // plan (uniform weights: the camera records' weights, no o_w / sg_w / cm_w).  robust_promote() gives every owned
+    // observation its own weights (o_w = o_w_base * sqrt(omega)) and keeps the maps from processing order to the
+    // slot-major (sg_map, -1: no slot) and camera-major (cm_map) copies; robust_reset() returns to the fresh handle.
+    bool pw = false;                    // the kernels read per-observation weights (o_w, sg_w, cm_w)
+    bool robust_on = false;
+    DevBuf<double> o_w_base, omega, rsel_hist_f, rsel_red, robust_r;
+    DevBuf<uint64_t> rs_bits, rsel_state;
+    DevBuf<int32_t> sg_map, cm_map;
+    DevBuf<unsigned> rsel_hist;
+    DevBuf<unsigned long long> rmax;
+    template <class T> static void dev_free(DevBuf<T> &b) { DevBuf<T> t; std::swap(t.p, b.p); b.n = 0; }
+    unsigned robust_grid() const { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(nobs, 256), 4096)); }
+    void robust_scratch() {             // what an evaluation needs (dbat_hip_robust_weights does not promote)
+        if (rs_bits.p || rsel_state.p) return;
+        rs_bits.alloc((size_t)std::max<int64_t>(nobs, 1));
+        robust_r.alloc((size_t)2 * std::max<int64_t>(P.no, 1));
+        rsel_hist.alloc(2 * RSEL_BINS); rsel_hist_f.alloc(2 * RSEL_BINS);
+        HIPCHK(hipMemset(rsel_hist.p, 0, 2 * RSEL_BINS * sizeof(unsigned)));
+        rsel_state.alloc(4); rmax.alloc(1); rsel_red.alloc((size_t)P.nranks);
+    }
+    void robust_promote() {
+        if (robust_on) return;
+        if (nobs >= ((int64_t)1 << 31) / 2) throw UsageError{"robust weights: more than 2^30 observations on one rank"};
+        robust_scratch();
+        const size_t n2 = (size_t)2 * std::max<int64_t>(nobs, 1);
+        o_w_base.alloc(n2);
+        if (P.uniform_w) {
+            o_w.alloc(n2); cm_w.alloc(n2);
+            if (use_sig) { sg_w.alloc(n2); HIPCHK(hipMemsetAsync(sg_w.p, 0, n2 * sizeof(double), stream)); }   // slots outside the groups stay 0
+            if (nobs > 0) launch<k_robust_base>(dim3(robust_grid()), dim3(256), 0, nobs, (const int32_t *)o_cam.p, (const double *)cam_w.p, o_w_base.p);
+        } else if (nobs > 0) {
+            HIPCHK(hipMemcpyAsync(o_w_base.p, o_w.p, (size_t)2 * nobs * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        }
+        {   // camera-major slot of every observation: the plan's stable counting sort by camera, tiled part first
+            std::vector<int32_t> cmm((size_t)nobs);
+            const int64_t ntiled = P.nb_tiled > 0 ? P.batch_start[P.nb_tiled] : 0;
+            std::vector<int64_t> cnt((size_t)P.nc + 1);
+            for (int part = 0; part < 2; ++part) {
+                const int64_t lo = part ? ntiled : 0, hi = part ? nobs : ntiled;
+                std::fill(cnt.begin(), cnt.end(), 0);
+                for (int64_t o = lo; o < hi; ++o) ++cnt[P.o_cam[o] + 1];
+                for (int c = 0; c < P.nc; ++c) cnt[c + 1] += cnt[c];
+                for (int64_t o = lo; o < hi; ++o) cmm[o] = (int32_t)(lo + cnt[P.o_cam[o]]++);
+            }
+            cm_map.upload(cmm);
+        }
+        if (use_sig) {   // slot-major slot: group g, slot j, point i at obs0_g + j*m_g + i (plan.hpp, signature groups)
+            std::vector<int32_t> sgm((size_t)nobs, -1);
+            for (size_t q = 0; q < P.sg_chunk.size() / 8; ++q) {
+                const int32_t *ch = &P.sg_chunk[8 * q];
+                const int64_t npts = ch[1], k = ch[2], m = ch[4], i0 = ch[5], g0 = ch[6];
+                for (int64_t i = i0; i < i0 + npts; ++i)
+                    for (int64_t j = 0; j < k; ++j) sgm[g0 + i * k + j] = (int32_t)(g0 + j * m + i);
+            }
+            sg_map.upload(sgm);
+        }
+        omega.alloc((size_t)std::max<int64_t>(nobs, 1));
+        robust_on = true; pw = true; d.o_w = o_w.p;
+        robust_set_ones();
+    }
+    void robust_apply_omega() {         // o_w, sg_w, cm_w from omega
+        if (nobs > 0)
+            launch<k_robust_apply<false>>(dim3(robust_grid()), dim3(256), 0, nobs, (const uint64_t *)nullptr, 1.0, 0, 1.0, omega.p, (const double *)o_w_base.p, o_w.p,
+                                          (const int32_t *)(use_sig ? sg_map.p : nullptr), sg_w.p, (const int32_t *)cm_map.p, cm_w.p);
+        s_valid = false;
+    }
+    void robust_set_ones() {
+        if (nobs > 0) launch<k_robust_fill>(dim3(robust_grid()), dim3(256), 0, nobs, 1.0, omega.p);
+        robust_apply_omega();
+    }
+    void robust_reset() {
+        if (robust_on) {
+            HIPCHK(hipStreamSynchronize(stream));
+            if (P.uniform_w) {
+                dev_free(o_w); dev_free(cm_w);
+                if (use_sig) dev_free(sg_w);
+                d.o_w = nullptr;
+            } else {             // the plan's weights, as init() uploaded them
+                HIPCHK(hipMemcpy(o_w.p, P.o_w.data(), P.o_w.size() * sizeof(double), hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(cm_w.p, P.cm_w.data(), P.cm_w.size() * sizeof(double), hipMemcpyHostToDevice));
+                if (use_sig) HIPCHK(hipMemcpy(sg_w.p, P.sg_w.data(), P.sg_w.size() * sizeof(double), hipMemcpyHostToDevice));
+            }
+            dev_free(o_w_base); dev_free(omega); dev_free(sg_map); dev_free(cm_map);
+            robust_on = false; pw = !P.uniform_w; s_valid = false;
+        }
+        dev_free(rs_bits); dev_free(robust_r); dev_free(rsel_hist); dev_free(rsel_hist_f); dev_free(rsel_state); dev_free(rmax); dev_free(rsel_red);
+    }
+    // max of one double over the ranks (the all-reduce sums: every rank contributes its own slot)
+    double max_over_ranks(double v) {
+        if (!multi()) return v;
+        std::vector<double> h((size_t)P.nranks, 0.0);
+        h[P.rank] = v;
+        HIPCHK(hipMemcpyAsync(rsel_red.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        do_allreduce(rsel_red.p, P.nranks);
+        HIPCHK(hipMemcpyAsync(h.data(), rsel_red.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return *std::max_element(h.begin(), h.end());
+    }
+    // exact median of s over all ranks' observations: radix select of the two middle order statistics
+    double robust_median() {
+        const uint64_t total = (uint64_t)P.no;
+        uint64_t st[4] = {0, 0, (total - 1) / 2, total / 2};
+        HIPCHK(hipMemcpyAsync(rsel_state.p, st, sizeof st, hipMemcpyHostToDevice, stream));
+        const unsigned gh = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(nobs, 4096), 1024));
+        for (int pass = 0; pass < RSEL_PASSES; ++pass) {
+            if (nobs > 0) launch<k_rsel_hist>(dim3(gh), dim3(256), 0, nobs, (const uint64_t *)rs_bits.p, (const uint64_t *)rsel_state.p, RSEL_SHIFT[pass], RSEL_BITS[pass], rsel_hist.p);
+            if (multi()) {
+                launch<k_rsel_to_f64>(dim3(16), dim3(256), 0, rsel_hist.p, rsel_hist_f.p);
+                do_allreduce(rsel_hist_f.p, 2 * RSEL_BINS);
+                launch<k_rsel_pick<true>>(dim3(1), dim3(256), 0, rsel_hist.p, (const double *)rsel_hist_f.p, rsel_state.p, RSEL_SHIFT[pass]);
+            } else {
+                launch<k_rsel_pick<false>>(dim3(1), dim3(256), 0, rsel_hist.p, (const double *)nullptr, rsel_state.p, RSEL_SHIFT[pass]);
+            }
+        }
+        HIPCHK(hipMemcpyAsync(st, rsel_state.p, sizeof st, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        double a, b;
+        memcpy(&a, &st[0], 8); memcpy(&b, &st[1], 8);
+        return (a + b) / 2.0;
+    }
+    // One evaluation at zz (collective): s of every owned observation (rs_bits), the scale, omega' and max |omega' -
+    // omega| over all ranks.  s_ip / omega_ip (device, [no], zero outside this rank's observations): optional.
+    void robust_eval(const double *zz, const dbat_hip_robust_options &ro, double *s_ip, double *omega_ip, double &scale, double &maxchg) {
+        robust_scratch();
+        HIPCHK(hipMemsetAsync(robust_r.p, 0, (size_t)2 * P.no * sizeof(double), stream));
+        eval_f(zz, nullptr, robust_r.p);
+        if (nobs > 0)
+            launch<k_robust_norm>(dim3(robust_grid()), dim3(256), 0, nobs, (const int64_t *)o_row.p, (const double *)robust_r.p,
+                                  (const double *)(robust_on ? o_w_base.p : (P.uniform_w ? nullptr : o_w.p)), (const int32_t *)o_cam.p, (const double *)cam_w.p, rs_bits.p, s_ip);
+        scale = 1.0;
+        if (ro.scale == DBAT_HIP_SCALE_MAD && P.no > 0) {
+            scale = robust_median() / ROBUST_MAD_C;
+            if (scale == 0.0) scale = 1.0;
+        }
+        HIPCHK(hipMemsetAsync(rmax.p, 0, sizeof(unsigned long long), stream));
+        if (nobs > 0)
+            launch<k_robust_weight>(dim3(robust_grid()), dim3(256), 0, nobs, (const uint64_t *)rs_bits.p, scale, (int)ro.loss, ro.k,
+                                    (const double *)(robust_on ? omega.p : nullptr), (const int64_t *)o_row.p, omega_ip, rmax.p);
+        unsigned long long mb = 0;
+        HIPCHK(hipMemcpyAsync(&mb, rmax.p, sizeof mb, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        memcpy(&maxchg, &mb, 8);
+        maxchg = max_over_ranks(maxchg);
+    }
+    // apply the omega' of the last evaluation (same scale and loss)
+    void robust_apply_eval(const dbat_hip_robust_options &ro, double scale) {
+        robust_promote();
+        if (nobs > 0)
+            launch<k_robust_apply<true>>(dim3(robust_grid()), dim3(256), 0, nobs, (const uint64_t *)rs_bits.p, scale, (int)ro.loss, ro.k, omega.p,
+                                         (const double *)o_w_base.p, o_w.p, (const int32_t *)(use_sig ? sg_map.p : nullptr), sg_w.p,
+                                         (const int32_t *)cm_map.p, cm_w.p);
+        s_valid = false;
+    }
+    // omega in IP order on every rank (1 everywhere on a handle that was not promoted)
+    void robust_omega_ip(double *host) {
+        if (!robust_on) { std::fill(host, host + P.no, 1.0); return; }
+        DevBuf<double> t;
+        t.alloc((size_t)std::max<int64_t>(P.no, 1));
+        HIPCHK(hipMemsetAsync(t.p, 0, (size_t)P.no * sizeof(double), stream));
+        if (nobs > 0) launch<k_scatter_rows1>(dim3(robust_grid()), dim3(256), 0, nobs, (const int64_t *)o_row.p, (const double *)omega.p, t.p);
+        if (multi()) do_allreduce(t.p, P.no);
+        HIPCHK(hipMemcpyAsync(host, t.p, (size_t)P.no * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
     }
     // ||J v||^2 and r'Jv at the linearisation point, ||v||^2 over owned entries
     void jtimes(const double *v, double &JvJv, double &rJv, double &vv) {
@@ -1921,11 +2089,18 @@ int dbat_hip_jacobian_csc(dbat_hip_handle *h, const double *x, int32_t weighted,
     // observations in REFERENCE row order (ascending IP column), so that the rows of a column ascend
     std::vector<int64_t> by_row((size_t)nobs);
     for (int64_t o = 0; o < nobs; ++o) by_row[P.o_row[o]] = o;
+    // reweighted observations (robust): the device's current weights, not the plan's
+    std::vector<double> ow_dev;
+    if (weighted && c.robust_on && nobs > 0) {
+        ow_dev.resize((size_t)2 * nobs);
+        HIPCHK(hipMemcpy(ow_dev.data(), c.o_w.p, ow_dev.size() * 8, hipMemcpyDeviceToHost));
+    }
+    const double *ow = ow_dev.empty() ? (P.uniform_w ? nullptr : P.o_w.data()) : ow_dev.data();
     for (int64_t k = 0; k < nobs; ++k) {
         const int64_t o = by_row[k];
         const int cam = P.o_cam[o];
         double w0 = 1.0, w1 = 1.0;
-        if (weighted) { w0 = P.uniform_w ? P.cam_w[2 * cam] : P.o_w[2 * o]; w1 = P.uniform_w ? P.cam_w[2 * cam + 1] : P.o_w[2 * o + 1]; }
+        if (weighted) { w0 = ow ? ow[2 * o] : P.cam_w[2 * cam]; w1 = ow ? ow[2 * o + 1] : P.cam_w[2 * cam + 1]; }
         cols_of(o, eo, io, iorow, nio, op);
         auto put = [&](int64_t col, double v0, double v1) {
             int64_t &f = fill[col];
@@ -2049,15 +2224,9 @@ int dbat_hip_jtimes(dbat_hip_handle *h, const double *v, double *Jv) {
     API_CATCH
 }
 
-int dbat_hip_solve(dbat_hip_handle *h, const dbat_hip_options *opt, double *x, dbat_hip_result *result,
-                   double *res, double *damp, double *aux, double *trace) {
-    API_TRY
-    if (!h || !opt || !x || !result) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    if (opt->damping < 0 || opt->damping > 3) { g_err = "Unknown damping"; return DBAT_HIP_EINVAL; }
-    if (opt->store_trace && !trace) { g_err = "store_trace without a trace buffer"; return DBAT_HIP_EINVAL; }
-    if (opt->term_fun && h->core->P.nranks > 1) { g_err = "term_fun: one-rank handles only (J*p rows stay with their shard)"; return DBAT_HIP_EUNSUPPORTED; }
-    Core &c = *h->core;
-    DeviceGuard dev_guard(c.device);
+namespace dbat {
+static void solve_once(Core &c, const dbat_hip_options *opt, double *x, dbat_hip_result *result, double *res, double *damp,
+                       double *aux, double *trace) {
     c.n_res_evals = c.n_lin = c.n_solves = c.n_trace_only = 0;
     c.trace_begin();
     c.x_to_z(x, c.z.p);
@@ -2100,6 +2269,144 @@ int dbat_hip_solve(dbat_hip_handle *h, const dbat_hip_options *opt, double *x, d
     result->sigma0 = std::sqrt(2 * out.f_final / dof);            // bundle.m:476-483
     result->n_residual_evals = c.n_res_evals; result->n_linearizations = c.n_lin; result->n_solves = c.n_solves;
     result->n_trace_only = c.n_trace_only;
+}
+
+static const char *solve_args_error(const dbat_hip_handle *h, const dbat_hip_options *opt, const double *x, const dbat_hip_result *result,
+                                    const double *trace, int &rc) {
+    rc = DBAT_HIP_EINVAL;
+    if (!h || !opt || !x || !result) return "null argument";
+    if (opt->damping < 0 || opt->damping > 3) return "Unknown damping";
+    if (opt->store_trace && !trace) return "store_trace without a trace buffer";
+    rc = DBAT_HIP_EUNSUPPORTED;
+    if (opt->term_fun && h->core->P.nranks > 1) return "term_fun: one-rank handles only (J*p rows stay with their shard)";
+    return nullptr;
+}
+
+static const char *robust_args_error(const dbat_hip_robust_options *ro) {
+    if (!ro) return "null argument";
+    if (ro->loss != DBAT_HIP_LOSS_HUBER && ro->loss != DBAT_HIP_LOSS_CAUCHY) return "robust: unknown loss";
+    if (!(ro->k > 0) || !std::isfinite(ro->k)) return "robust: k must be positive and finite";
+    if (ro->scale != DBAT_HIP_SCALE_APRIORI && ro->scale != DBAT_HIP_SCALE_MAD) return "robust: unknown scale";
+    if (ro->max_outer < 1 || ro->max_outer >= DBAT_HIP_ROBUST_MAX_OUTER) return "robust: max_outer out of range";
+    if (!(ro->weight_tol >= 0) || !std::isfinite(ro->weight_tol)) return "robust: weight_tol must be finite and >= 0";
+    return nullptr;
+}
+}  // namespace dbat
+
+int dbat_hip_solve(dbat_hip_handle *h, const dbat_hip_options *opt, double *x, dbat_hip_result *result,
+                   double *res, double *damp, double *aux, double *trace) {
+    API_TRY
+    int rc;
+    if (const char *e = solve_args_error(h, opt, x, result, trace, rc)) { g_err = e; return rc; }
+    Core &c = *h->core;
+    DeviceGuard dev_guard(c.device);
+    solve_once(c, opt, x, result, res, damp, aux, trace);
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+int dbat_hip_default_robust_options(int32_t loss, dbat_hip_robust_options *ropt) {
+    if (!ropt || (loss != DBAT_HIP_LOSS_HUBER && loss != DBAT_HIP_LOSS_CAUCHY)) { g_err = "bad loss"; return DBAT_HIP_EINVAL; }
+    ropt->loss = loss;
+    ropt->k = loss == DBAT_HIP_LOSS_HUBER ? 1.5 : 2.385;
+    ropt->scale = DBAT_HIP_SCALE_APRIORI;
+    ropt->max_outer = 10;
+    ropt->weight_tol = 1e-3;
+    return DBAT_HIP_OK;
+}
+
+int dbat_hip_robust_weights(dbat_hip_handle *h, const double *x, const dbat_hip_robust_options *ropt,
+                            double *omega, double *s_norm, double *scale) {
+    API_TRY
+    if (!h || !x || !omega) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    if (const char *e = robust_args_error(ropt)) { g_err = e; return DBAT_HIP_EINVAL; }
+    Core &c = *h->core;
+    const Plan &P = c.P;
+    DeviceGuard dev_guard(c.device);
+    c.x_to_z(x, c.zt.p);
+    DevBuf<double> om, sn;
+    om.alloc((size_t)std::max<int64_t>(P.no, 1));
+    HIPCHK(hipMemsetAsync(om.p, 0, (size_t)P.no * sizeof(double), c.stream));
+    if (s_norm) {
+        sn.alloc((size_t)std::max<int64_t>(P.no, 1));
+        HIPCHK(hipMemsetAsync(sn.p, 0, (size_t)P.no * sizeof(double), c.stream));
+    }
+    double sc = 1.0, chg = 0.0;
+    c.robust_eval(c.zt.p, *ropt, sn.p, om.p, sc, chg);
+    if (c.multi()) {
+        c.do_allreduce(om.p, P.no);
+        if (s_norm) c.do_allreduce(sn.p, P.no);
+    }
+    HIPCHK(hipMemcpyAsync(omega, om.p, (size_t)P.no * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    if (s_norm) HIPCHK(hipMemcpyAsync(s_norm, sn.p, (size_t)P.no * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipStreamSynchronize(c.stream));
+    if (scale) *scale = sc;
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+int dbat_hip_set_obs_weights(dbat_hip_handle *h, const double *omega) {
+    API_TRY
+    if (!h) { g_err = "null handle"; return DBAT_HIP_EINVAL; }
+    Core &c = *h->core;
+    const Plan &P = c.P;
+    DeviceGuard dev_guard(c.device);
+    if (!omega) { c.robust_reset(); return DBAT_HIP_OK; }
+    for (int64_t i = 0; i < P.no; ++i)
+        if (!(omega[i] > 0.0 && omega[i] <= 1.0)) {
+            g_err = "dbat_hip_set_obs_weights: omega[" + std::to_string(i) + "] is not in (0, 1]";
+            return DBAT_HIP_EINVAL;
+        }
+    c.robust_promote();
+    if (c.nobs > 0) {           // processing order of this rank's observations
+        std::vector<double> om((size_t)c.nobs);
+        for (int64_t k = 0; k < c.nobs; ++k) om[k] = omega[P.o_row[k]];
+        HIPCHK(hipMemcpy(c.omega.p, om.data(), om.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    c.robust_apply_omega();
+    HIPCHK(hipStreamSynchronize(c.stream));
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+int dbat_hip_solve_robust(dbat_hip_handle *h, const dbat_hip_options *opt, const dbat_hip_robust_options *ropt,
+                          double *x, dbat_hip_result *result, double *res, double *damp, double *aux, double *trace,
+                          dbat_hip_robust_result *rr, double *omega_out) {
+    API_TRY
+    int rc;
+    if (const char *e = solve_args_error(h, opt, x, result, trace, rc)) { g_err = e; return rc; }
+    if (!rr) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    if (const char *e = robust_args_error(ropt)) { g_err = e; return DBAT_HIP_EINVAL; }
+    Core &c = *h->core;
+    DeviceGuard dev_guard(c.device);
+    memset(rr, 0, sizeof *rr);
+    auto t0 = std::chrono::steady_clock::now();
+    auto rw_clock = [&]() {
+        const auto now = std::chrono::steady_clock::now();
+        rr->reweight_s += std::chrono::duration<double>(now - t0).count();
+    };
+    c.robust_promote();
+    c.robust_set_ones();
+    HIPCHK(hipStreamSynchronize(c.stream));
+    rw_clock();
+    solve_once(c, opt, x, result, res, damp, aux, trace);
+    rr->inner_iters[0] = result->iters;
+    rr->outer = 1;
+    for (int t = 1; t <= ropt->max_outer && result->code == 0; ++t) {
+        t0 = std::chrono::steady_clock::now();
+        c.x_to_z(x, c.zt.p);
+        double sc = 1.0, chg = 0.0;
+        c.robust_eval(c.zt.p, *ropt, nullptr, nullptr, sc, chg);
+        rr->scale[t - 1] = sc;
+        rr->max_change = chg;
+        if (chg <= ropt->weight_tol) { rr->converged = 1; rw_clock(); break; }
+        c.robust_apply_eval(*ropt, sc);
+        HIPCHK(hipStreamSynchronize(c.stream));
+        rw_clock();
+        solve_once(c, opt, x, result, res, damp, aux, trace);
+        rr->inner_iters[rr->outer++] = result->iters;
+    }
+    if (omega_out) c.robust_omega_ip(omega_out);
     return DBAT_HIP_OK;
     API_CATCH
 }

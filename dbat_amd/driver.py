@@ -62,8 +62,47 @@ def _parse_args(args):
     return o
 
 
+MAD_C = 1.1774100225154747          # sqrt(2 ln 2): the median of a chi_2-distributed norm (robust scale 'mad')
+ROBUST_K = {'huber': 1.5, 'cauchy': 2.385}
+
+
+def robust_weight_fn(u, loss, k):
+    """The weight factor omega(u) in (0, 1] of the robust losses (u = s / scale >= 0): Huber 1 for u <= k, else k / u;
+    Cauchy 1 / (1 + (u / k)^2).  Host statement of what dbat_hip_solve_robust applies on the device."""
+    u = np.asarray(u, float)
+    if loss == 'huber':
+        return np.where(u <= k, 1.0, k / np.where(u <= k, 1.0, u))
+    if loss == 'cauchy':
+        t = u / k
+        return 1.0 / (1.0 + t * t)
+    raise BadInput("robust: unknown loss '%s' (None, 'huber' or 'cauchy')" % (loss,))
+
+
+def _robust_args(robust, robust_k, robust_scale, robust_max_outer, robust_tol):
+    """Checks bundle()'s robust arguments (before any device work): None or (loss, k, scale, max_outer, tol)."""
+    if robust is None:
+        return None
+    if not isinstance(robust, str) or robust.lower() not in ROBUST_K:
+        raise BadInput("bundle: robust must be None, 'huber' or 'cauchy', not %r" % (robust,))
+    loss = robust.lower()
+    k = ROBUST_K[loss] if robust_k is None else robust_k
+    if isinstance(k, bool) or not isinstance(k, (int, float, np.integer, np.floating)) or not np.isfinite(k) or k <= 0:
+        raise BadInput('bundle: robust_k must be a positive finite number, not %r' % (robust_k,))
+    if not isinstance(robust_scale, str) or robust_scale.lower() not in _hip.SCALE:
+        raise BadInput("bundle: robust_scale must be 'apriori' or 'mad', not %r" % (robust_scale,))
+    if (isinstance(robust_max_outer, bool) or not isinstance(robust_max_outer, (int, np.integer))
+            or not 1 <= robust_max_outer < _hip.ROBUST_MAX_OUTER):
+        raise BadInput('bundle: robust_max_outer must be an integer in [1, %d], not %r'
+                       % (_hip.ROBUST_MAX_OUTER - 1, robust_max_outer))
+    if (isinstance(robust_tol, bool) or not isinstance(robust_tol, (int, float, np.integer, np.floating))
+            or not np.isfinite(robust_tol) or robust_tol < 0):
+        raise BadInput('bundle: robust_tol must be a finite number >= 0, not %r' % (robust_tol,))
+    return loss, float(k), robust_scale.lower(), int(robust_max_outer), float(robust_tol)
+
+
 def bundle(s, *args, device=None, comm=None, store_trace=True, jacobian=False, deterministic=False,
-           term_fun=None, veto_fun=None, reuse_handle=True):
+           term_fun=None, veto_fun=None, reuse_handle=True, robust=None, robust_k=None, robust_scale='apriori',
+           robust_max_outer=10, robust_tol=1e-3):
     """[s,ok,iters,s0,E] = bundle(s[,maxIter][,damping][,'trace'][,tol]
     [,'absterm'][,'singulartest'|'nosingulartest'][,veto][,'pmdof'][,'dofverb'])
 
@@ -78,7 +117,21 @@ def bundle(s, *args, device=None, comm=None, store_trace=True, jacobian=False, d
     the two function handles of the reference's solver interface, for callers that used the solvers directly.
     `reuse_handle=False` builds (and destroys) a handle of its own instead of using the cached one (_hip.acquire).
     The returned struct shares the arrays bundle() does not change (IP.*, masks, blocks) with its input.
+
+    Robust estimation (iteratively reweighted least squares over the image points, dbat_hip_solve_robust):
+    `robust='huber' | 'cauchy'` down-weights image points with large residuals.  Per outer step the weight factor
+    omega of every IP column comes from u = s / scale, s the norm of its two residuals weighted by IP.std, scale 1
+    (`robust_scale='apriori'`) or median(s) / sqrt(2 ln 2) ('mad'); robust_weight_fn gives omega(u) (`robust_k`:
+    default 1.5 / 2.385).  Both rows then have the sigma IP.std / sqrt(omega).  The loop solves with omega = 1,
+    then reweights and solves again from the result until max |omega' - omega| <= `robust_tol` or
+    `robust_max_outer` reweightings; code, iterations, sigma0 and the trace are the last solve's.  E.robust holds
+    loss, k, scale_mode, scale (per reweighting evaluation), weights (omega per IP column), outer (solves),
+    converged, inner_iters, max_change, downweighted (IP columns with omega < 0.5, by omega ascending) and
+    reweight_time.  The robust loop takes no term_fun / veto_fun and prints no live 'trace'.
     """
+    ro = _robust_args(robust, robust_k, robust_scale, robust_max_outer, robust_tol)
+    if ro is not None and (term_fun is not None or veto_fun is not None):
+        raise BadInput('bundle: robust=... takes no term_fun / veto_fun')
     o = _parse_args(args)
     if o['veto']:
         # bundle.m:169 references an undefined function `chirality`
@@ -126,7 +179,11 @@ def bundle(s, *args, device=None, comm=None, store_trace=True, jacobian=False, d
         opt.store_trace = int(bool(store_trace))
         # 'trace': the solver's own line per iteration, printed while the loop runs (gauss_newton_armijo.m:119-128 ...)
         live = (lambda *a: print(_hip.trace_text(*a), flush=True)) if o['doTrace'] and rank == 0 else None
-        x, res, rr, damp, aux, T = h.solve(x0, opt, term_fun=term_fun, veto_fun=veto_fun, trace_fun=live)   # complete on every rank of a sharded run
+        if ro is None:
+            x, res, rr, damp, aux, T = h.solve(x0, opt, term_fun=term_fun, veto_fun=veto_fun, trace_fun=live)   # complete on every rank of a sharded run
+        else:
+            ropt = _hip.robust_options(ro[0], ro[1], ro[2], ro[3], ro[4])
+            x, res, rr, damp, aux, T, rres, omega = h.solve_robust(x0, opt, ropt)
         t_host.append(time.perf_counter())
         E = NS(maxIter=o['maxIter'], convTol=o['convTol'], absTerm=o['absTerm'],
                singularTest=o['singularTest'], chirality=False)
@@ -148,6 +205,14 @@ def bundle(s, *args, device=None, comm=None, store_trace=True, jacobian=False, d
             E.damping = NS(name='lmp', delta=damp, rho=rho, delta0=float(np.linalg.norm(x0)),
                            rhoBad=opt.rho_bad, rhoGood=opt.rho_good, step=step)
         E.res, E.trace, E.time = rr, T, res.time_s
+        E.robust = None
+        if ro is not None:
+            n_eval = rres.outer - 1 + rres.converged
+            low = np.flatnonzero(omega < 0.5)
+            E.robust = NS(loss=ro[0], k=ro[1], scale_mode=ro[2], scale=np.array(rres.scale[:n_eval]), weights=omega,
+                          outer=int(rres.outer), converged=bool(rres.converged),
+                          inner_iters=np.array(rres.inner_iters[:rres.outer]), max_change=float(rres.max_change),
+                          downweighted=low[np.argsort(omega[low], kind='stable')], reweight_time=float(rres.reweight_s))
         # where it went (hipEvent stage timers of the library), the E.time of bundle.m:287-294 by stage
         E.timeStages = dict(zip(('linearise', 'factor_solve', 'backsub', 'residual', 'other'), [float(v) for v in res.stage_s]))
         E.code, E.usedIters = int(res.code), int(res.iters)
@@ -276,6 +341,7 @@ def bundle_cov(s, E, *names, device=0):
     h = _hip.acquire(s, device)          # the handle bundle() left behind, with the values of its result: one plan for both
     done = False
     try:
+        _reapply_weights(h, E)
         if dense and h.n > CXX_MAX_N:
             raise BadInput("bundle_cov: '%s' is an n x n dense matrix and n = %d (offered up to %d unknowns; "
                            "'CIO', 'CEO', 'COP' give the blocks at any size)" % (dense[0].upper(), h.n, CXX_MAX_N))
@@ -364,12 +430,13 @@ def reliability_critical(alpha0=0.001, beta0=0.80):
               delta0=float(normal + z.inv_cdf(beta0)))
 
 
-def reliability_stats(s, rw, qvv, r_prior, maps, alpha0=0.001, beta0=0.80):
+def reliability_stats(s, rw, qvv, r_prior, maps, alpha0=0.001, beta0=0.80, omega=None):
     """The statistics of bundle_reliability from the pieces of Qvv = I - J inv(J'J) J' (pure host function).
     rw       (m,) weighted residuals (E.final.weighted.r)
     qvv      (3, nObs) r_u, q_uv, r_v of every image point (IP column order)
     r_prior  (m - 2 nObs,) redundancy numbers of the prior rows, in the row order of rw
     maps     (IOix, EOix, OPix) x index of every IO / EO / OP entry, -1 = not an unknown (Handle.index_maps)
+    omega    (nObs,) weight factors of a robust bundle (E.robust.weights) or None: the MDB uses IP.std / sqrt(omega)
     Returns the struct bundle_reliability documents."""
     rw = np.asarray(rw, float)
     no = s.IP.val.shape[1]
@@ -385,6 +452,8 @@ def reliability_stats(s, rw, qvv, r_prior, maps, alpha0=0.001, beta0=0.80):
     sq = np.sqrt(np.where(ok, rIP, 1.0))
     w = np.where(ok, v / sq, np.nan)
     std = np.broadcast_to(np.asarray(s.IP.std, float), (2, no))
+    if omega is not None:
+        std = std / np.sqrt(np.asarray(omega, float).reshape(1, no))
     mdb = np.where(ok, crit.delta0 * std / sq, np.inf)
     # T = v' Qvv^-1 v, chi^2(2) under H0 (a singular 2 x 2 block: undefined)
     det = ru * rv - quv * quv
@@ -431,9 +500,20 @@ def bundle_reliability(s, E, alpha0=0.001, beta0=0.80, device=0):
     h = _hip.acquire(s, device)          # the handle bundle() left behind, with the values of its result
     done = False
     try:
+        rob = _reapply_weights(h, E)
         qvv, rp = h.redundancy(np.asarray(E.x, float))
         maps = h.index_maps()
         done = True
     finally:
         _hip.release(h, keep=done)
-    return reliability_stats(s, E.final.weighted.r, qvv, rp, maps, crit.alpha0, crit.beta0)
+    return reliability_stats(s, E.final.weighted.r, qvv, rp, maps, crit.alpha0, crit.beta0,
+                             omega=None if rob is None else rob.weights)
+
+
+def _reapply_weights(h, E):
+    """A robust bundle's weight factors on an acquired handle (acquire() -> set_values restored the base weights):
+    covariance and redundancy then describe the final reweighted system.  Returns E.robust."""
+    rob = getattr(E, 'robust', None)
+    if rob is not None:
+        h.set_obs_weights(rob.weights)
+    return rob

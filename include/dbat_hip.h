@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DBAT_HIP_ABI_VERSION 5   /* 5: dbat_hip_redundancy; 4: dbat_hip_options grew (trace_fun); dbat_hip_structure_key / dbat_hip_handle_key / dbat_hip_set_values; dbat_hip_bench_step ms[16], dbat_hip_info [24]; 3: dbat_hip_options grew (term_fun, veto_fun); 2: dbat_hip_result grew (stage_s, n_trace_only); dbat_hip_info [16]; dbat_hip_bench_step ms[12] */
+#define DBAT_HIP_ABI_VERSION 5   /* 5: dbat_hip_redundancy; additive: dbat_hip_robust_weights / dbat_hip_set_obs_weights / dbat_hip_solve_robust; 4: dbat_hip_options grew (trace_fun); dbat_hip_structure_key / dbat_hip_handle_key / dbat_hip_set_values; dbat_hip_bench_step ms[16], dbat_hip_info [24]; 3: dbat_hip_options grew (term_fun, veto_fun); 2: dbat_hip_result grew (stage_s, n_trace_only); dbat_hip_info [16]; dbat_hip_bench_step ms[12] */
 
 /* error returns */
 #define DBAT_HIP_OK            0
@@ -480,6 +480,62 @@ int  dbat_hip_posterior_cov(dbat_hip_handle *h, const double *x, double sigma0, 
  * (as dbat_hip_posterior_cov).  On a sharded handle (collective) every rank computes the blocks of
  * its own observations and all ranks receive everything. */
 int  dbat_hip_redundancy(dbat_hip_handle *h, const double *x, double *qvv_ip, double *r_prior);
+
+/* ---- robust estimation: iteratively reweighted least squares over the image points -------------------------------
+ * For image point i (one IP column, two rows) at parameters x:
+ *   s_i   = ||(w_u v_u, w_v v_v)||_2, w = 1 / (IP.std * pxSize) the BASE weights, v the unweighted residual
+ *   scale = 1 (DBAT_HIP_SCALE_APRIORI) or median(s) / sqrt(2 ln 2) (DBAT_HIP_SCALE_MAD: the exact median over all
+ *           image points, the mean of the two middle values for an even count; 1 if it is 0)
+ *   u_i   = s_i / scale;  omega_i in (0, 1]:  Huber  1 for u <= k, else k / u  (default k = 1.5)
+ *                                            Cauchy 1 / (1 + (u / k)^2)      (default k = 2.385)
+ * Both rows of image point i then carry the weight w * sqrt(omega_i) (effective sigma IP.std / sqrt(omega_i)).
+ * Prior observations are never reweighted.  A handle that never sees one of the calls below allocates nothing
+ * for them; dbat_hip_set_values and dbat_hip_set_obs_weights(h, NULL) restore the base weights and the
+ * uniform-weight path of a fresh handle exactly. */
+#define DBAT_HIP_LOSS_HUBER    0
+#define DBAT_HIP_LOSS_CAUCHY   1
+#define DBAT_HIP_SCALE_APRIORI 0
+#define DBAT_HIP_SCALE_MAD     1
+#define DBAT_HIP_ROBUST_MAX_OUTER 64   /* capacity of dbat_hip_robust_result's per-step arrays */
+
+typedef struct dbat_hip_robust_options {
+    int32_t loss;           /* DBAT_HIP_LOSS_* */
+    double  k;              /* tuning constant (> 0) */
+    int32_t scale;          /* DBAT_HIP_SCALE_* */
+    int32_t max_outer;      /* reweighting steps after the first solve, 1 .. DBAT_HIP_ROBUST_MAX_OUTER - 1; default 10 */
+    double  weight_tol;     /* stop when max |omega' - omega| <= weight_tol; default 1e-3 */
+} dbat_hip_robust_options;
+
+typedef struct dbat_hip_robust_result {
+    int32_t outer;          /* inner solves run (1 + reweighting steps applied) */
+    int32_t converged;      /* 1: the weights settled within weight_tol */
+    int32_t inner_iters[DBAT_HIP_ROBUST_MAX_OUTER];   /* iterations of every inner solve */
+    double  scale[DBAT_HIP_ROBUST_MAX_OUTER];         /* scale of every reweighting evaluation (outer entries at most) */
+    double  max_change;     /* max |omega' - omega| of the last evaluation */
+    double  reweight_s;     /* wall seconds spent in the reweighting evaluations and applications */
+} dbat_hip_robust_result;
+
+/* defaults for a loss: k = 1.5 (Huber) or 2.385 (Cauchy), apriori scale, max_outer 10, weight_tol 1e-3 */
+int  dbat_hip_default_robust_options(int32_t loss, dbat_hip_robust_options *ropt);
+
+/* One reweighting evaluation at x, not applied: omega [n_obs] and, if not NULL, s_norm [n_obs] in IP column order,
+ * and the scale.  On a sharded handle (collective) every rank receives the full vectors. */
+int  dbat_hip_robust_weights(dbat_hip_handle *h, const double *x, const dbat_hip_robust_options *ropt,
+                             double *omega, double *s_norm, double *scale);
+
+/* Sets omega [n_obs] (IP column order) directly: every value finite and in (0, 1], else DBAT_HIP_EINVAL.  NULL:
+ * back to the base weights and the path of a fresh handle. */
+int  dbat_hip_set_obs_weights(dbat_hip_handle *h, const double *omega);
+
+/* The IRLS outer loop: omega = 1, solve (dbat_hip_solve with opt); then up to max_outer times: evaluate omega' at
+ * x; stop (converged = 1) if max |omega' - omega| <= weight_tol, keeping the omega of the last solve; else apply
+ * omega' and solve again from x.  A nonzero code of an inner solve ends the loop.  result, res, damp, aux, trace
+ * are those of the last inner solve, as dbat_hip_solve gives them (sigma0: the reweighted one); the handle keeps
+ * the weights of the last solve (dbat_hip_final_residuals, dbat_hip_redundancy use them).  omega_out [n_obs] (IP
+ * column order, may be NULL): those weights.  Collective on a sharded handle. */
+int  dbat_hip_solve_robust(dbat_hip_handle *h, const dbat_hip_options *opt, const dbat_hip_robust_options *ropt,
+                           double *x, dbat_hip_result *result, double *res, double *damp, double *aux, double *trace,
+                           dbat_hip_robust_result *rr, double *omega_out);
 
 #ifdef __cplusplus
 }

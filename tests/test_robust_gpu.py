@@ -1,0 +1,210 @@
+"""Robust bundle() on the device (dbat_hip_robust_weights / set_obs_weights / solve_robust): one reweighting
+evaluation against NumPy from the oracle's residuals (exact MAD median), the IRLS loop against the host restatement
+of test_robust_cpu, the promoted per-observation path against the plain solve, blunder recovery, handle reuse and
+reliability after a robust bundle, the build routes, deterministic mode and 2 / 4 ranks."""
+import os
+
+import numpy as np
+import pytest
+
+from helpers import camcal_struct, relerr, sxb_prior_eo_struct, synth_struct
+from test_reliability_cpu import _oracle_setup
+from test_robust_cpu import blundered, oracle_irls, oracle_s_norm, oracle_scale
+from dbat_amd.driver import robust_weight_fn
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module')
+def hip():
+    from dbat_amd import _hip
+    import torch
+    assert torch.cuda.is_available(), 'gpu tests need a GPU'
+    _hip.load()
+    return _hip
+
+
+def _drop_last_ip(s):
+    """The struct without its last image point (an odd count where the scene has an even one)."""
+    no = s.IP.val.shape[1]
+    for nm in list(vars(s.IP)):
+        a = getattr(s.IP, nm)
+        if isinstance(a, np.ndarray) and a.ndim >= 1 and a.shape[-1] == no:
+            setattr(s.IP, nm, a[..., :no - 1].copy())
+    return s
+
+
+def _scenes():
+    return [('tiny-' + v, lambda v=v: synth_struct('tiny', v)[0]) for v in ('plain', 'selfcal', 'imagevar', 'priors', 'groups4')] + \
+        [('tiny-plain-odd', lambda: _drop_last_ip(synth_struct('tiny', 'plain')[0])),
+         ('camcal', camcal_struct), ('sxb-prior-eo', lambda: sxb_prior_eo_struct(True)[0])]
+
+
+@pytest.mark.parametrize('name,make', _scenes(), ids=[n for n, _ in _scenes()])
+def test_weights_at_x0_match_numpy(hip, name, make):
+    s = make()
+    so, x0, w = _oracle_setup(s)
+    no = s.IP.val.shape[1]
+    sn_o = oracle_s_norm(so, x0, w, no)
+    h = hip.Handle(s)
+    try:
+        for loss, sm in (('huber', 'apriori'), ('cauchy', 'mad'), ('huber', 'mad')):
+            ro = hip.robust_options(loss, scale=sm)
+            om, sn, sc = h.robust_weights(x0, ro)
+            assert np.abs(sn - sn_o).max() <= 1e-12 * max(sn_o.max(), 1e-300), name
+            if sm == 'mad':
+                assert sc == np.median(sn) / np.sqrt(2 * np.log(2)), (name, sc)
+            else:
+                assert sc == 1.0
+            # the weight kernel on its own s exactly as the definition; against the oracle's s to the slope of omega
+            assert np.abs(om - robust_weight_fn(sn / sc, loss, ro.k)).max() <= 1e-12, name
+            assert np.abs(om - robust_weight_fn(sn_o / oracle_scale(sn_o, sm), loss, ro.k)).max() <= 1e-11, name
+    finally:
+        h.close()
+    assert name != 'tiny-plain-odd' or no % 2 == 1
+    assert name != 'tiny-plain' or no % 2 == 0
+
+
+# tolerances chosen so that the last two weight changes of the host loop lie well away from them (huber: 7.6e-2,
+# 3.9e-4; cauchy: 9.8e-4, 1.1e-4): the stopping step cannot flip on rounding
+IRLS_CASES = [('huber', 'apriori', 10, 4e-3), ('cauchy', 'apriori', 10, 3e-4), ('cauchy', 'mad', 3, 1e-3)]
+
+
+@pytest.mark.parametrize('loss,sm,mo,tol', IRLS_CASES, ids=['%s-%s' % c[:2] for c in IRLS_CASES])
+def test_irls_matches_host_restatement(hip, loss, sm, mo, tol):
+    from dbat_amd import bundle
+    s = blundered('tiny')
+    k = {'huber': 1.5, 'cauchy': 2.385}[loss]
+    xo, omo, outo, convo, scales, chgo, codeo = oracle_irls(s, loss, k, sm, max_outer=mo, tol=tol)
+    assert codeo == 0 and outo >= 2
+    assert chgo < tol / 2 if convo else chgo > 10 * tol
+    res, ok, iters, s0, E = bundle(s, 'gna', robust=loss, robust_scale=sm, robust_max_outer=mo, robust_tol=tol)
+    R = E.robust
+    assert ok and R.outer == outo and R.converged == convo
+    assert relerr(E.x, xo) <= 1e-7
+    assert np.abs(R.weights - omo).max() <= 1e-8
+    assert np.allclose(R.scale, scales, rtol=1e-9, atol=0) and len(R.inner_iters) == R.outer
+    assert set(R.downweighted.tolist()) >= {5, 40, 77}
+    assert np.all(np.diff(R.weights[R.downweighted]) >= 0)
+
+
+def test_huge_k_is_the_plain_solve_on_the_promoted_path(hip):
+    from dbat_amd import bundle
+    s = synth_struct('tiny', 'plain')[0]
+    _, ok0, it0, s00, E0 = bundle(s, 'gna', reuse_handle=False)
+    _, ok, it, s0, E = bundle(s, 'gna', robust='huber', robust_k=1e30, reuse_handle=False)
+    assert ok0 and ok and E.robust.outer == 1 and E.robust.converged and E.robust.max_change == 0.0
+    assert np.all(E.robust.weights == 1.0) and E.robust.downweighted.size == 0
+    assert relerr(E.x, E0.x) <= 1e-10 and abs(s0 - s00) <= 1e-10 * s00
+
+
+def _err(res, truth, pts):
+    return (np.sqrt(np.mean((np.asarray(res.OP.val)[:, pts] - truth['OP'][:, pts]) ** 2)),
+            np.sqrt(np.mean((np.asarray(res.EO.val)[:3] - truth['EO'][:3]) ** 2)))
+
+
+def test_blunder_recovery_small(hip):
+    from dbat_amd import bundle
+    s, truth = synth_struct('small', 'plain', seed=3)
+    no = s.IP.val.shape[1]
+    rng = np.random.default_rng(7)
+    bad = np.sort(rng.choice(no, no // 100, replace=False))
+    sb = synth_struct('small', 'plain', seed=3)[0]
+    sb.IP.val = np.array(sb.IP.val, float)
+    ang = rng.uniform(0, 2 * np.pi, bad.size)
+    std = np.asarray(sb.IP.std, float)
+    sb.IP.val[0, bad] += 20 * std[0, bad] * np.cos(ang)
+    sb.IP.val[1, bad] += 20 * std[1, bad] * np.sin(ang)
+    rc, okc, *_ = bundle(s, 'gna')
+    rp, okp, *_ = bundle(sb, 'gna')
+    rr, okr, _, _, E = bundle(sb, 'gna', robust='cauchy', robust_scale='mad')
+    assert okc and okp and okr
+    # The error against truth is dominated by the datum of the synthetic scene (about 0.19 RMS with or without the
+    # blunders), so the blunders' effect is measured against the clean scene's solution, over the points they touch:
+    # the plain solve moves them, the robust one keeps them (nearly) where the clean data put them.
+    hit = np.unique(np.asarray(sb.IP.pt)[bad])
+    dev = lambda r: np.sqrt(np.mean((np.asarray(r.OP.val)[:, hit] - np.asarray(rc.OP.val)[:, hit]) ** 2))
+    dp, dr = dev(rp), dev(rr)
+    assert dp > 0 and dr <= dp / 3, (dp, dr)
+    ec, er = _err(rc, truth, hit), _err(rr, truth, hit)
+    assert er[0] <= 1.5 * ec[0] and er[1] <= 1.5 * ec[1], (ec, er)
+    w = E.robust.weights
+    clean = np.setdiff1d(np.arange(no), bad)
+    assert np.all(w[bad] < 0.1)
+    assert np.count_nonzero(w[clean] < 0.1) <= 0.005 * clean.size
+
+
+def test_handle_reuse_and_reliability_after_robust(hip):
+    from dbat_amd import _hip, bundle, bundle_reliability
+    s = blundered('tiny')
+    _, ok, _, _, Er = bundle(s, 'gna', robust='cauchy')
+    assert ok
+    # deterministic sums: two handles give the same bits only with them
+    _, ok1, it1, s01, E1 = bundle(s, 'gna', deterministic=True)      # the cached handle, robust before
+    assert _hip.cache_stats['last'] == 'hit'
+    _, ok2, it2, s02, E2 = bundle(s, 'gna', deterministic=True, reuse_handle=False)
+    assert ok1 and ok2 and it1 == it2 and s01 == s02
+    assert np.array_equal(E1.x, E2.x) and np.array_equal(E1.final.weighted.r, E2.final.weighted.r)
+    # reliability of the reweighted system: its residuals, sum r = m - n
+    res, ok, _, _, Er = bundle(s, 'gna', robust='cauchy')
+    no = s.IP.val.shape[1]
+    ru = Er.final.unweighted.r[:2 * no].reshape(no, 2)
+    rw = Er.final.weighted.r[:2 * no].reshape(no, 2)
+    wb = 1.0 / (np.asarray(s.IP.std, float).T * np.asarray(s.IO.sensor.pxSize, float)[:, s.IP.cam].T)
+    assert np.allclose(rw, ru * wb * np.sqrt(Er.robust.weights)[:, None], rtol=1e-12, atol=1e-300)
+    rel = bundle_reliability(res, Er)
+    assert abs(rel.total - (Er.numObs - Er.numParams)) <= 1e-9 * Er.numObs
+    assert np.all(rel.IP.mdb[:, [5, 40, 77]] > 3 * np.median(rel.IP.mdb))
+
+
+def _route_run(s, env, **kw):
+    from dbat_amd import bundle
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return bundle(s, 'gna', reuse_handle=False, **kw)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def test_routes_agree(hip):
+    s = blundered('tiny')
+    runs = [_route_run(s, {'DBAT_HIP_SIG': v}, robust='huber') for v in ('0', '1', '2')]
+    for r in runs[1:]:
+        assert r[4].robust.outer == runs[0][4].robust.outer
+        assert relerr(r[4].x, runs[0][4].x) <= 1e-9 and np.abs(r[4].robust.weights - runs[0][4].robust.weights).max() <= 1e-9
+    c = camcal_struct()
+    runs = [_route_run(c, {'DBAT_HIP_HEAVY': v}, robust='huber') for v in ('0', '1')]
+    assert runs[0][1] and runs[1][1] and runs[0][4].robust.outer == runs[1][4].robust.outer
+    assert relerr(runs[1][4].x, runs[0][4].x) <= 1e-9
+    assert np.abs(runs[1][4].robust.weights - runs[0][4].robust.weights).max() <= 1e-9
+
+
+def test_deterministic_robust_is_bit_identical(hip):
+    from dbat_amd import bundle
+    s = blundered('tiny')
+    a = bundle(s, 'gna', deterministic=True, robust='cauchy', robust_scale='mad', robust_max_outer=4)
+    b = bundle(s, 'gna', deterministic=True, robust='cauchy', robust_scale='mad', robust_max_outer=4)
+    assert np.array_equal(a[4].x, b[4].x) and a[3] == b[3]
+    assert np.array_equal(a[4].robust.weights, b[4].robust.weights) and np.array_equal(a[4].robust.scale, b[4].robust.scale)
+
+
+@pytest.mark.parametrize('world', [2, 4])
+def test_ranks_match_single(hip, world):
+    from dbat_amd import bundle
+    from test_multishard_gpu import _run_ranks
+    s = blundered('small', idx=(3, 500, 1200, 7000, 20000))
+    r1 = bundle(s, 'gna', robust='cauchy', robust_scale='mad', robust_max_outer=4, reuse_handle=False)
+    out, _ = _run_ranks(s, world, lambda comm: bundle(s, 'gna', comm=comm, robust='cauchy', robust_scale='mad',
+                                                      robust_max_outer=4))
+    for r in out:
+        E, E1 = r[4], r1[4]
+        assert E.robust.outer == E1.robust.outer
+        # (x of the ranks differs from one rank's in the 1e-10 range: omega follows it to ~1e-12)
+        assert np.abs(E.robust.weights - E1.robust.weights).max() <= 1e-11
+        assert np.allclose(E.robust.scale, E1.robust.scale, rtol=1e-11, atol=0)
+        assert relerr(E.x, E1.x) <= 1e-9
