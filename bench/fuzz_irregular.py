@@ -1,5 +1,6 @@
 """Randomised sweep of the paths that regular synthetic scenes never reach, outside the test-suite: irregular
-visibility (random observations dropped, down to two rays per point), control points seen in many or all images
+visibility (random observations dropped, down to two rays per point; in some scenes points cut down to one ray, fixed
+or held by priors), control points seen in many or all images
 (heavy and giant points: k_heavy_z / k_heavy_z_giant / k_heavy_syrk of csrc/heavy.hpp, or the column-list kernels), cameras per
 tile, batch length and giant-kernel width forced small, signature kernels on / off -- the device's Gauss-Newton and
 damped steps, step scalars, gradient and (small scenes) the posterior covariance blocks against the oracle.
@@ -56,8 +57,32 @@ def irregular_scene(sd):
     hk = int(rng.integers(0, 4))
     if hk == 0: env['DBAT_HIP_HEAVY'] = '0'
     elif hk == 1: env['DBAT_HIP_HEAVY_KS'] = str(rng.choice(['1', '3', '7']))
-    desc = '%3d cams %4d pts %2d rays, %d obs (max %3d per point), selfcal=%d groups=%d, drop %.1f, %s' % (
-        cams, points, rays, len(cam), int(np.bincount(pt).max()), selfcal, groups, drop, ' '.join('%s=%s' % (k[9:], v) for k, v in env.items()) or 'defaults')
+    # single-ray points, in a third of the scenes (a generator of their own: the draws above stay those of earlier sweeps):
+    # a fraction of the ordinary points cut down to one ray, fixed or held by a prior on all three coordinates -- up to
+    # 256 points per 256 observations, so batches close on the point cap (Plan::PMAX) instead
+    rs = np.random.default_rng(21000 + sd)
+    single = ''
+    if rs.integers(0, 3) == 0:
+        kind = str(rs.choice(['fixed', 'prior3']))
+        cnt = np.bincount(pt, minlength=points)
+        cut = (cnt >= 2) & (cnt <= rays) & (rs.random(points) < float(rs.choice([0.7, 0.95])))
+        o1 = np.lexsort((rs.random(len(pt)), pt))           # one observation of every point drawn at random: its first here
+        one = np.zeros(len(pt), bool); one[o1[np.r_[True, pt[o1][1:] != pt[o1][:-1]]]] = True
+        keep = ~cut[pt] | one
+        s.IP.val, s.IP.std = s.IP.val[:, keep], s.IP.std[:, keep]
+        s.IP.cam, s.IP.pt = cam[keep], pt[keep]
+        sel = np.flatnonzero(cut)
+        if kind == 'fixed':
+            s.OP.val[:, sel] = truth['OP'][:, sel]
+            s.bundle.est.OP[:, sel] = False
+        else:
+            s.prior.OP.use[:, sel] = True
+            s.prior.OP.std[:, sel] = 0.02
+            s.prior.OP.val[:, sel] = truth['OP'][:, sel] + rs.normal(0, 0.02, (3, len(sel)))
+        single = ', %d single-ray %s' % (len(sel), kind)
+    desc = '%3d cams %4d pts %2d rays, %d obs (max %3d per point)%s, selfcal=%d groups=%d, drop %.1f, %s' % (
+        cams, points, rays, len(s.IP.cam), int(np.bincount(pt).max()), single, selfcal, groups, drop,
+        ' '.join('%s=%s' % (k[9:], v) for k, v in env.items()) or 'defaults')
     return s, env, desc
 
 

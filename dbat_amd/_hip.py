@@ -182,6 +182,7 @@ SYMBOLS = {
 DEBUG_SYMBOLS = {
     'dbat_hip_debug_plan_digest': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_uint64), C.c_int32, C.c_char_p, C.c_int32]),
     'dbat_hip_debug_heavy_plan_selftest': (C.c_int, [C.POINTER(Problem), _dp]),
+    'dbat_hip_debug_batch_stats': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_int64)]),
     'dbat_hip_debug_model_eval_host': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_double,
                                                  _dp, _dp, _dp, _dp, _dp, _dp]),
 }
@@ -821,6 +822,21 @@ def heavy_plan_selftest(s, shard_rank=0, shard_count=1):
     check(lib.dbat_hip_debug_heavy_plan_selftest(C.byref(p), dptr(out)))
     return dict(on=bool(out[0]), points=int(out[1]), row_groups=int(out[2]), tasks=int(out[3]), ksteps=int(out[4]),
                 max_diff=float(out[5]), max_abs=float(out[6]), entries=int(out[7]))
+
+
+def batch_stats(s, shard_rank=0, shard_count=1):
+    """Host-only (debug): the sizes of the plan's batches (dbat_hip_debug_batch_stats).  'tiled' and 'untiled' (the
+    batches after the tiles: heavy points, or every batch when nothing is tiled): the most points and the most
+    observations of one batch, the batches closed by the point cap PMAX rather than by BT, the most batches of one tile;
+    then BT, PMAX, the plan's cap of batches per tile and the number of batches of either kind."""
+    lib = load()
+    p, keep = problem_from_struct(s, 0, shard_rank, shard_count)
+    a = (C.c_int64 * 16)()
+    check(lib.dbat_hip_debug_batch_stats(C.byref(p), a))
+    v = [int(x) for x in a]
+    part = lambda q: dict(max_points=v[q], max_obs=v[q + 1], closed_by_cap=v[q + 2], max_tile_batches=v[q + 3])
+    return dict(tiled=part(0), untiled=part(4), BT=v[8], PMAX=v[9], tile_bmax=v[10], n_batches_tiled=v[11],
+                n_batches_untiled=v[12])
 
 
 def plan_domain_map(s, shard_count):

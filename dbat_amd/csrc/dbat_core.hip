@@ -398,8 +398,10 @@ struct Core {
         lds_cov = ((size_t)P.BT * P.ncolmax * 3 + (size_t)P.BT * 6) * sizeof(double);
         // wave-specialised tile kernel: 256-observation batches, 16-point chunks, 2 panels
         tile2_pc = TILE2_PC;
-        lds_tile2 = ((size_t)TILE2_NBUF * 3 * tile2_pc * TILE_LD + (size_t)256 * 9 + (size_t)128 * 15 + TILE_LD) * sizeof(double);
-        lds_tile3 = ((size_t)TILE3_NBUF * 3 * TILE3_PC * TILE_LD + (size_t)256 * 9 + (size_t)256 * 9 + TILE_LD) * sizeof(double);
+        // per point of a batch (Plan::PMAX): tile2 B'B | B'r of two batches and V^-1 | g | R; tile3 both of two producer groups
+        static_assert(Plan::PMAX == 256 / 2, "k_build_tile2 / k_build_tile3 lay out NPROD / 2 points per batch");
+        lds_tile2 = ((size_t)TILE2_NBUF * 3 * tile2_pc * TILE_LD + (size_t)2 * Plan::PMAX * 9 + (size_t)Plan::PMAX * 15 + TILE_LD) * sizeof(double);
+        lds_tile3 = ((size_t)TILE3_NBUF * 3 * TILE3_PC * TILE_LD + (size_t)2 * Plan::PMAX * 9 + (size_t)2 * Plan::PMAX * 9 + TILE_LD) * sizeof(double);
         use_tile2 = P.BT == 256 && P.ncolmax <= 15;      // (the plan does not tile anything else)
         // fixed IO: the tile kernel with two producer groups (it holds at most 64 batch offsets per tile, the plan's
         // cap is 48); self-calibration: k_build_tile2
@@ -2809,6 +2811,32 @@ int dbat_hip_debug_heavy_plan_selftest(const dbat_hip_problem *prob, double *out
     }
     out[0] = 1; out[1] = P.hv_npts; out[2] = P.hv_ngroups; out[3] = P.hv_ntasks; out[4] = (double)nks_all;
     out[5] = dmax; out[6] = vmax; out[7] = (double)ncmp;
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+/* Host only (debug / CPU unit tests): the sizes of the batches of the plan.  out[16]: for the tiled batches {most points
+ * of one batch, most observations of one batch, batches closed by Plan::PMAX rather than by BT, most batches of one
+ * tile}, the same four for the batches after the tiles (heavy points; every batch when nothing is tiled; the last
+ * entry 0), then {BT, Plan::PMAX, the plan's cap of batches per tile, tiled batches, untiled batches}, zeros. */
+int dbat_hip_debug_batch_stats(const dbat_hip_problem *prob, int64_t *out) {
+    API_TRY
+    if (!prob || !out) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    Plan P;
+    if (!build_plan(*prob, P, true)) { g_err = P.err; return DBAT_HIP_EINVAL; }
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    const int64_t nb = (int64_t)P.batch_start.size() - 1;
+    for (int64_t b = 0; b < nb; ++b) {
+        const int64_t o0 = P.batch_start[b], o1 = P.batch_start[b + 1];
+        if (o1 <= o0) continue;
+        int64_t *st = out + (b < P.nb_tiled ? 0 : 4);
+        st[0] = std::max<int64_t>(st[0], (int64_t)P.o_pidx[o1 - 1] + 1);
+        st[1] = std::max<int64_t>(st[1], o1 - o0);
+    }
+    out[2] = P.nb_pcap[0]; out[6] = P.nb_pcap[1];
+    for (size_t t = 0; P.nb_tiled > 0 && t + 1 < P.tile_batch.size(); ++t)
+        out[3] = std::max<int64_t>(out[3], P.tile_batch[t + 1] - P.tile_batch[t]);
+    out[8] = P.BT; out[9] = Plan::PMAX; out[10] = P.tile_bmax; out[11] = P.nb_tiled; out[12] = nb - P.nb_tiled;
     return DBAT_HIP_OK;
     API_CATCH
 }

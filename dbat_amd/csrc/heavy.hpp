@@ -23,6 +23,7 @@
 // the flush, 8 bytes per element of a pair's blocks and task.
 #pragma once
 #include "kernels.hpp"
+#include "plan.hpp"
 
 namespace dbat {
 
@@ -43,10 +44,10 @@ struct HeavyDev {
 };
 constexpr int HV_NIOC = 9;
 
-// dynamic LDS of k_heavy_z: [256][9] per-observation terms | [128][9] per-point blocks | the IO rows of the batch's points
+// dynamic LDS of k_heavy_z: [256][9] per-observation terms | [Plan::PMAX][9] per-point blocks | the IO rows of the batch's points
 // (slots x 3, self-calibration) | deterministic mode: [256][3 (NCX - 6)] the observations' shares of the IO rows
 __host__ __device__ constexpr size_t heavy_z_lds_bytes(int ncx, int max_batch_slots, bool deterministic) {
-    return ((size_t)256 * 9 + (size_t)128 * 9 + (ncx > 6 ? (size_t)3 * max_batch_slots + (deterministic ? (size_t)256 * 3 * (ncx - 6) : 0) : 0)) * sizeof(double);
+    return ((size_t)256 * 9 + (size_t)Plan::PMAX * 9 + (ncx > 6 ? (size_t)3 * max_batch_slots + (deterministic ? (size_t)256 * 3 * (ncx - 6) : 0) : 0)) * sizeof(double);
 }
 
 // The point's block: priors, squared column norms, damping, R (V^-1 = R R'), pivots, y = R'g -- as k_build.
@@ -106,10 +107,10 @@ __global__ __launch_bounds__(256) void k_heavy_z(DevProblem d, HeavyDev hv, cons
     constexpr int NQ = NCX - 6;                      // IO columns of one camera at most
     extern __shared__ double smem[];
     double *red = smem;                              // [256][9]  B'B (6) | B'r (3) of every observation
-    double *pinfo = red + 256 * 9;                   // [128][9]  per point: V | g, then R | y
-    double *zsum = pinfo + 128 * 9;                  // [IO slots of the batch][3]  the IO rows of Z
+    double *pinfo = red + 256 * 9;                   // [PMAX][9]  per point: V | g, then R | y
+    double *zsum = pinfo + Plan::PMAX * 9;           // [IO slots of the batch][3]  the IO rows of Z
     constexpr int WS = 3 * (NQ > 0 ? NQ : 1);
-    __shared__ int pseg[128];                        // per point of the batch: first lane | observations << 16
+    __shared__ int pseg[Plan::PMAX];                 // per point of the batch: first lane | observations << 16
     __shared__ unsigned char lio[256][NQ > 0 ? NQ : 1];
     __shared__ double sh[8];
     const int t = threadIdx.x;

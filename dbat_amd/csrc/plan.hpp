@@ -63,6 +63,11 @@ struct Plan {
     uvec<uint32_t> o_seg;                   // (seg_start | seg_len<<16) within batch
     uvec<int64_t> o_row;                    // IP column (reference order)
     std::vector<int64_t> batch_start;              // [nb+1]
+    // points of one batch at most: the per-point LDS of k_build_tile2, k_build_tile3 and k_heavy_z.  Points with two
+    // or more rays never pass it (BT / 2); points seen in one image would put up to BT into a batch
+    static constexpr int PMAX = 128;
+    int64_t nb_pcap[2] = {0, 0};                   // batches closed by PMAX, not by BT: tiled, untiled (debug statistics)
+    int tile_bmax = 0;                             // batches per tile at most
     // tiles: runs of batches whose observations touch at most CMAX cameras; the
     // Schur complement of a tile is accumulated in LDS and flushed once
     uvec<uint8_t> o_lc;                     // local camera index of every observation
@@ -1348,6 +1353,10 @@ inline bool build_plan(const dbat_hip_problem &pb, Plan &P, bool with_obs) {
     const int bmax_floor = std::max(1, env_int("DBAT_HIP_TILE_BMIN", 2));     // (round 4: 4 -> 2; the reference's roma project: tile kernel 0.136 -> 0.084 ms)
     const int bmax_auto = (int)std::min<int64_t>(48, std::max<int64_t>(bmax_floor, (shard_obs / std::max(1, P.BT) + 511) / 512));
     const int tile_bmax = bmax_auto;
+    P.tile_bmax = tile_bmax;
+    P.nb_pcap[0] = P.nb_pcap[1] = 0;
+    // the point closes the open batch: its observations do not fit, or the batch holds PMAX points already
+    auto batch_full = [&](int k) { return pos > bstart && (pos - bstart + k > P.BT || pidx >= Plan::PMAX); };
     for (int64_t i = P.pt_lo; i < P.pt_hi; ++i) {
         const int64_t is = i - P.pt_lo;
         const int k = kk[is];
@@ -1394,9 +1403,9 @@ inline bool build_plan(const dbat_hip_problem &pb, Plan &P, bool with_obs) {
                 }
             }
             // a tile is one workgroup's work: cap its length, otherwise a long run of points seen
-            // by the same few cameras becomes the tail of the whole launch
+            // by the same few cameras becomes the tail of the whole launch (batches closed on BT or on PMAX alike)
             const int64_t tile_nb = (int64_t)P.batch_start.size() - 1 - P.tile_batch.back();   // closed batches
-            const bool too_long = pos - bstart + k > P.BT && tile_nb + 1 >= tile_bmax;
+            const bool too_long = batch_full(k) && tile_nb + 1 >= tile_bmax;
             const bool over = (int)cur_cams.size() + fresh > P.CMAX ||
                               (int)cur_io.size() + fresh_io > Plan::IOT || too_long;
             if (over && pos > tile_first_obs) {
@@ -1407,7 +1416,10 @@ inline bool build_plan(const dbat_hip_problem &pb, Plan &P, bool with_obs) {
                 ++tile_id;
             }
         }
-        if (pos - bstart + k > P.BT) { P.batch_start.push_back(pos); bstart = pos; }
+        if (batch_full(k)) {
+            if (pos - bstart + k <= P.BT) ++P.nb_pcap[in_heavy || !P.CMAX ? 1 : 0];
+            P.batch_start.push_back(pos); bstart = pos;
+        }
         if (pos == bstart) pidx = 0;
         if (P.CMAX && !in_heavy) {                   // same cameras as the previous point of the tile: same group
             bool same = g_npts > 0 && (int)g_cams.size() == k && g_npts < (1 << 20);
@@ -1443,6 +1455,10 @@ inline bool build_plan(const dbat_hip_problem &pb, Plan &P, bool with_obs) {
         P.nb_tiled = (int64_t)P.batch_start.size() - 1;
     }
     if (!P.CMAX) P.nb_tiled = 0;
+    // k_build_tile2 / k_build_tile3 hold the batch offsets of at most 64 batches of a tile
+    for (size_t t = 0; P.CMAX && t + 1 < P.tile_batch.size(); ++t)
+        if (P.tile_batch[t + 1] - P.tile_batch[t] > 64)
+            return fail(P, "internal: a tile of " + std::to_string(P.tile_batch[t + 1] - P.tile_batch[t]) + " batches (at most 64)");
     lapt("decisions: batches, tiles, signature groups (one thread)");
     // ---- the copies that depend on the decisions
     par.run(n_sh, [&](int64_t lo_, int64_t hi_, int) {

@@ -259,6 +259,86 @@ def synth_struct(name='tiny', variant='plain', seed=None):
     return s, truth
 
 
+CROWDED_KINDS = ('fixed', 'prior3', 'zprior', 'zfixed')
+
+
+def crowded_struct(kind, frac=0.85, cams=60, points=3000, control=0, selfcal=False, seed=None):
+    """Scene whose batches hold many points: synth.make_scene('small', rays=2) with a fraction `frac` of the points cut
+    down to ONE ray (the observation kept is drawn at random).  A single ray fixes two of a point's three coordinates, so
+    those points are made determined by `kind`:
+       'fixed'   all three coordinates fixed at their true values (a control point measured in one image)
+       'prior3'  a prior observation of all three coordinates, estimated
+       'zprior'  a prior of Z only, X and Y estimated (mono-plotting with a height prior)
+       'zfixed'  Z fixed at its true value, X and Y estimated (mono-plotting on a known height)
+    With 'zprior' and 'zfixed' every fourth of these points is fixed instead: such points say nothing of X and Y, and
+    two-ray tie points do not carry the scale from one stereo pair to the next, so the block needs control points.
+    control > 0: one more point, at the middle of the block, seen in the `control` cameras nearest to it, with a prior
+    on all three coordinates -- with DBAT_HIP_CMAX below `control` it is heavy, and the other points, being few, join
+    it on the heavy route.  Returns (s, truth)."""
+    from dbat_amd import synth
+    if kind not in CROWDED_KINDS:
+        raise ValueError(kind)
+    s, truth = synth.make_scene('small', cams=cams, points=points, rays=2, selfcal=selfcal, seed=seed)
+    rng = np.random.default_rng(4321)
+    npnt = s.OP.val.shape[1]
+    single = rng.random(npnt) < frac
+    # the point's two observations: drop one of them at random
+    pt = np.asarray(s.IP.pt)
+    order = np.argsort(pt, kind='stable')
+    first = np.ones(len(pt), bool)
+    first[order[1::2]] = False                          # every point has exactly two observations, ascending
+    drop_second = rng.random(npnt) < 0.5
+    drop = single[pt] & (first == ~drop_second[pt])
+    keep = ~drop
+    IP = s.IP
+    IP.val, IP.std = np.asfortranarray(IP.val[:, keep]), np.asfortranarray(IP.std[:, keep])
+    IP.cam, IP.pt = IP.cam[keep], IP.pt[keep]
+    est, pr, OPt = s.bundle.est.OP, s.prior.OP, truth['OP']
+    sel = np.flatnonzero(single)
+    if kind == 'fixed':
+        s.OP.val[:, sel] = OPt[:, sel]
+        est[:, sel] = False
+    elif kind == 'prior3':
+        pr.use[:, sel] = True
+        pr.std[:, sel] = np.array([[0.02], [0.02], [0.03]])
+        pr.val[:, sel] = OPt[:, sel] + rng.normal(0, 1, (3, len(sel))) * pr.std[:, sel]
+    elif kind == 'zprior':
+        pr.use[2, sel] = True
+        pr.std[2, sel] = 0.03
+        pr.val[2, sel] = OPt[2, sel] + rng.normal(0, 0.03, len(sel))
+    else:
+        s.OP.val[2, sel] = OPt[2, sel]
+        est[2, sel] = False
+    if kind in ('zprior', 'zfixed'):
+        ctl = sel[::4]
+        s.OP.val[:, ctl] = OPt[:, ctl]
+        est[:, ctl] = False
+        pr.use[:, ctl] = False
+    if control:
+        IO, EO = truth['IO'], truth['EO']
+        Q = np.array([[EO[0].mean()], [EO[1].mean()], [5.0]])
+        cams_c = np.sort(np.argsort(np.hypot(EO[0] - Q[0, 0], EO[1] - Q[1, 0]))[:control]).astype(IP.cam.dtype)
+        OPx = np.hstack([OPt, Q])
+        px = float(np.ravel(s.IO.sensor.pxSize)[0])
+        uv, depth = synth.project(IO, EO, OPx, cams_c, np.full(control, npnt), px, nK=3, nP=2)
+        assert np.all(depth < 0), 'control point behind a camera'
+        uv = uv + rng.normal(0, 0.5, uv.shape)
+        s.OP.val = np.asfortranarray(np.hstack([s.OP.val, Q + rng.normal(0, 0.05, (3, 1))]))
+        s.OP.id = np.append(s.OP.id, s.OP.id.max() + 1)
+        s.bundle.est.OP = np.asfortranarray(np.hstack([est, np.ones((3, 1), bool)]))
+        pr.use = np.asfortranarray(np.hstack([pr.use, np.ones((3, 1), bool)]))
+        pr.std = np.asfortranarray(np.hstack([pr.std, np.full((3, 1), 0.01)]))
+        pr.val = np.asfortranarray(np.hstack([pr.val, Q + rng.normal(0, 0.01, (3, 1))]))
+        truth['OP'] = OPx
+        cam = np.concatenate([IP.cam, cams_c])
+        pt_ = np.concatenate([IP.pt, np.full(control, npnt, IP.pt.dtype)])
+        o = np.lexsort((pt_, cam))                      # image-major, ascending OP inside an image
+        IP.val = np.asfortranarray(np.hstack([IP.val, uv])[:, o])
+        IP.std = np.asfortranarray(np.hstack([IP.std, np.ones((2, control))])[:, o])
+        IP.cam, IP.pt = cam[o], pt_[o]
+    return s, truth
+
+
 def relerr(a, b):
     """misc/relerr.m: Frobenius relative error."""
     a, b = np.asarray(a, float), np.asarray(b, float)
