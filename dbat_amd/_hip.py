@@ -173,6 +173,8 @@ SYMBOLS = {
     'dbat_hip_chol_stats': (C.c_int, [_H, C.POINTER(C.c_int64)]),
     'dbat_hip_posterior_cov': (C.c_int, [_H, _dp, C.c_double, _dp, _dp, _dp, _dp]),
     'dbat_hip_redundancy': (C.c_int, [_H, _dp, _dp, _dp]),
+    'dbat_hip_ray_angles': (C.c_int, [_H, _dp, _dp, _dp, _ip, _ip]),
+    'dbat_hip_debug_ray_angles_host': (C.c_int, [C.POINTER(Problem), _dp, _dp]),
     'dbat_hip_default_robust_options': (C.c_int, [C.c_int32, C.POINTER(RobustOptions)]),
     'dbat_hip_robust_weights': (C.c_int, [_H, _dp, C.POINTER(RobustOptions), _dp, _dp, _dp]),
     'dbat_hip_set_obs_weights': (C.c_int, [_H, _dp]),
@@ -185,6 +187,7 @@ DEBUG_SYMBOLS = {
     'dbat_hip_debug_batch_stats': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_int64)]),
     'dbat_hip_debug_model_eval_host': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_double,
                                                  _dp, _dp, _dp, _dp, _dp, _dp]),
+    'dbat_hip_debug_ray_angles_ms': (C.c_int, [_H, _dp, C.POINTER(C.c_int64)]),
 }
 
 _lib = None
@@ -604,6 +607,26 @@ class Handle:
         check(self.lib.dbat_hip_redundancy(self.h, dptr(x), dptr(qvv), dptr(rp)))
         return qvv[:3 * no].reshape(3, no, order='F'), rp[:self.m - 2 * no]
 
+    def ray_angles(self, x):
+        """Ray intersection angles at x (dbat_hip_ray_angles): (op, cam, op_rays, cam_rays) -- the largest angle
+        [rad] between two rays of every object point and of every image (0 for one ray, NaN for none) and the
+        numbers of rays.  DbatHipError on a handle that is one shard of several."""
+        x = np.ascontiguousarray(x, float)
+        nc, npnt = int(self.prob.n_images), int(self.prob.n_points)
+        op, cam = np.zeros(max(npnt, 1)), np.zeros(max(nc, 1))
+        opr, camr = np.zeros(max(npnt, 1), np.int32), np.zeros(max(nc, 1), np.int32)
+        check(self.lib.dbat_hip_ray_angles(self.h, dptr(x), dptr(op), dptr(cam), opr.ctypes.data_as(_ip),
+                                           camr.ctypes.data_as(_ip)))
+        return op[:npnt], cam[:nc], opr[:npnt], camr[:nc]
+
+    def ray_angles_ms(self):
+        """Device-event milliseconds of the last ray_angles (debug): point kernels, unit directions of the images,
+        pair kernel + acos; and the matrix-core instructions (256 pairs each) and workgroups of the pair kernel."""
+        ms, info = np.zeros(3), (C.c_int64 * 2)()
+        check(self.lib.dbat_hip_debug_ray_angles_ms(self.h, dptr(ms), info))
+        return dict(points=float(ms[0]), cam_dirs=float(ms[1]), cam_pairs=float(ms[2]), mfma=int(info[0]),
+                    workgroups=int(info[1]))
+
     def robust_weights(self, x, ropt):
         """One reweighting evaluation at x, not applied (dbat_hip_robust_weights): (omega, s_norm, scale), the two
         vectors per IP column."""
@@ -868,3 +891,13 @@ def debug_model_eval_host(model, nK, nP, EO6, IO, px, Q, uv):
     check(lib.dbat_hip_debug_model_eval_host(model, nK, nP, dptr(a[0]), dptr(a[1]), float(px),
                                              dptr(a[2]), dptr(a[3]), dptr(r), dptr(A), dptr(B), dptr(Cc)))
     return r, A.reshape(6, 2).T, B.reshape(3, 2).T, Cc.reshape(R, 2).T
+
+
+def debug_ray_angles_host(s):
+    """Host evaluation of the definition of dbat_hip_ray_angles over the struct's own values (no GPU needed):
+    (op, cam) in radians."""
+    lib = load()
+    p, keep = problem_from_struct(s)
+    op, cam = np.zeros(max(int(p.n_points), 1)), np.zeros(max(int(p.n_images), 1))
+    check(lib.dbat_hip_debug_ray_angles_host(C.byref(p), dptr(op), dptr(cam)))
+    return op[:int(p.n_points)], cam[:int(p.n_images)]

@@ -25,6 +25,7 @@
 #include "plan.hpp"
 #include "resect.hpp"
 #include "robust.hpp"
+#include "angles.hpp"
 
 namespace dbat {
 
@@ -1231,6 +1232,122 @@ struct Core {
         }
         HIPCHK(hipMemcpyAsync(hqvv, qvv.p, (size_t)3 * P.no * sizeof(double), hipMemcpyDeviceToHost, stream));
         sync();
+    }
+    // ---- ray intersection angles at zt (angles.hpp).  What the kernels need beyond the plan's uploads -- where every
+    // point's observations start, where every image's observations are in the camera-major copy, the work items of the
+    // pair kernel, the scratch array of unit directions -- is built by the first call and kept; a handle that never
+    // asks for angles has none of it.  The point side follows the plan's classification: the tiled points (at most
+    // CMAX rays) take the lane-group kernel, everything after the tiled batches (heavy and giant points; every point
+    // where nothing is tiled) a workgroup each.
+    struct AnglePlan {
+        bool ready = false;
+        int32_t hp0 = 0, hp1 = 0;                        // heavy / giant points: [hp0, hp1) of the processing order
+        int32_t heavy_kmax = 0;
+        int64_t n_items = 0, n_slots = 0, n_mfma = 0;
+        std::vector<int32_t> op_rays, cam_rays;          // per point (caller's order), per image
+        DevBuf<int64_t> pt_pos, cam_src, cam_pad;
+        DevBuf<int32_t> items;
+        DevBuf<double> cdir, op_out, cam_out;
+        DevBuf<unsigned long long> cam_min;
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        double ms[3] = {0, 0, 0};                        // last call: point kernels, directions of the images, pair kernel + finish
+        ~AnglePlan() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+    } ang;
+    void angle_plan() {
+        if (ang.ready) return;
+        const int64_t npt = P.np, no = nobs;
+        std::vector<int64_t> pos((size_t)npt + 1, 0);
+        for (int64_t o = 0; o < no; ++o) ++pos[(size_t)P.o_pt[o] + 1];
+        ang.op_rays.assign((size_t)npt, 0);
+        for (int64_t r = 0; r < npt; ++r) ang.op_rays[P.porder[r]] = (int32_t)pos[r + 1];
+        for (int64_t r = 0; r < npt; ++r) pos[r + 1] += pos[r];
+        const int64_t ho0 = P.batch_start[std::min<int64_t>(P.nb_tiled, nb)];
+        ang.hp1 = no > 0 ? P.o_pt[no - 1] + 1 : 0;
+        ang.hp0 = ho0 < no ? P.o_pt[ho0] : ang.hp1;
+        ang.heavy_kmax = 0;
+        for (int64_t r = 0; r < ang.hp0; ++r)
+            if (pos[r + 1] - pos[r] > ANG_LIGHT_KMAX) throw DeviceError{"internal: a tiled point with more rays than the angle kernel holds"};
+        for (int64_t r = ang.hp0; r < ang.hp1; ++r) ang.heavy_kmax = (int32_t)std::max<int64_t>(ang.heavy_kmax, pos[r + 1] - pos[r]);
+        if (ang.heavy_kmax > ANG_HEAVY_KMAX)
+            throw UsageError{"ray angles: an object point with " + std::to_string(ang.heavy_kmax) + " rays (at most " + std::to_string(ANG_HEAVY_KMAX) + ")"};
+        // images: their ranges in the two parts of the camera-major copy, 16-direction tiles, work items
+        std::vector<int64_t> src((size_t)4 * P.nc, 0), pad((size_t)P.nc + 1, 0);
+        for (int64_t q = 0; q < n_cm_chunks_all; ++q) {
+            const int c = P.cm_chunk_cam[q];
+            const int64_t len = P.cm_chunk_start[q + 1] - P.cm_chunk_start[q];
+            int64_t *sc = src.data() + 4 * (size_t)c;        // {first tiled, tiled, first of the rest, all}
+            if (q < n_cm_chunks) {
+                if (sc[1] == 0) sc[0] = P.cm_chunk_start[q];
+                sc[1] += len;
+            } else if (sc[3] == sc[1]) sc[2] = P.cm_chunk_start[q];   // (the chunks of the tiled part all come first)
+            sc[3] += len;
+        }
+        ang.cam_rays.assign((size_t)P.nc, 0);
+        std::vector<int32_t> items;
+        ang.n_mfma = 0;
+        for (int c = 0; c < P.nc; ++c) {
+            const int64_t n = src[4 * (size_t)c + 3];
+            if (n >= ((int64_t)1 << 31) - 16) throw UsageError{"ray angles: an image with more than 2^31 points"};
+            ang.cam_rays[c] = (int32_t)n;
+            const int64_t T = (n + 15) / 16;
+            pad[(size_t)c + 1] = pad[c] + 16 * T;
+            if (n >= 2) {
+                for (int64_t I0 = 0; I0 < T; I0 += ANG_RUN) { items.push_back(c); items.push_back((int32_t)I0); }
+                ang.n_mfma += T * (T + 1) / 2;
+            }
+        }
+        ang.n_items = (int64_t)items.size() / 2;
+        ang.n_slots = pad[P.nc];
+        ang.pt_pos.upload(pos); ang.cam_src.upload(src); ang.cam_pad.upload(pad); ang.items.upload(items);
+        ang.cdir.alloc((size_t)3 * std::max<int64_t>(ang.n_slots, 1));
+        ang.op_out.alloc((size_t)std::max<int64_t>(npt, 1)); ang.cam_out.alloc((size_t)std::max(P.nc, 1));
+        ang.cam_min.alloc((size_t)std::max(P.nc, 1));
+        for (auto &e : ang.ev) HIPCHK(hipEventCreate(&e));
+        ang.ready = true;
+    }
+    void ray_angles(double *hop, double *hcam, int32_t *hop_rays, int32_t *hcam_rays) {
+        angle_plan();
+        if (hop_rays) std::copy(ang.op_rays.begin(), ang.op_rays.end(), hop_rays);
+        if (hcam_rays) std::copy(ang.cam_rays.begin(), ang.cam_rays.end(), hcam_rays);
+        if (!hop && !hcam) return;
+        prep_cams(zt.p);
+        const double *zz = zt.p;
+        HIPCHK(hipEventRecord(ang.ev[0], stream));
+        if (hop) {
+            if (ang.hp0 > 0)
+                launch<k_angles_pt_light>(dim3((unsigned)cdiv(ang.hp0, ANG_LIGHT_PTS)), dim3(256), 0, zz, (int64_t)P.NS, cams.p, o_cam.p, ang.pt_pos.p, ang.hp0, ang.op_out.p);
+            if (ang.hp1 > ang.hp0)
+                launch<k_angles_pt_heavy>(dim3((unsigned)(ang.hp1 - ang.hp0)), dim3(256), (size_t)3 * ang.heavy_kmax * sizeof(double), zz, (int64_t)P.NS, cams.p,
+                                          o_cam.p, ang.pt_pos.p, ang.hp0, ang.heavy_kmax, ang.op_out.p);
+        }
+        HIPCHK(hipEventRecord(ang.ev[1], stream));
+        if (hcam) {
+            HIPCHK(hipMemsetAsync(ang.cam_min.p, 0xFF, (size_t)P.nc * sizeof(unsigned long long), stream));
+            if (ang.n_slots > 0)
+                launch<k_angles_cam_dirs>(dim3((unsigned)cdiv(ang.n_slots, 256)), dim3(256), 0, zz, (int64_t)P.NS, cams.p, P.nc, cm_pt.p, ang.cam_src.p, ang.cam_pad.p, ang.cdir.p);
+        }
+        HIPCHK(hipEventRecord(ang.ev[2], stream));
+        if (hcam) {
+            if (ang.n_items > 0)
+                launch<k_angles_cam_pairs>(dim3((unsigned)ang.n_items), dim3(256), 0, ang.cdir.p, ang.cam_pad.p, ang.items.p, ang.cam_min.p);
+            launch<k_angles_cam_finish>(dim3((unsigned)cdiv(P.nc, 256)), dim3(256), 0, P.nc, ang.cam_src.p, ang.cam_min.p, ang.cam_out.p);
+        }
+        HIPCHK(hipEventRecord(ang.ev[3], stream));
+        std::vector<double> tmp;
+        if (hop && ang.hp1 > 0) {
+            tmp.resize((size_t)ang.hp1);
+            HIPCHK(hipMemcpyAsync(tmp.data(), ang.op_out.p, (size_t)ang.hp1 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        }
+        if (hcam) HIPCHK(hipMemcpyAsync(hcam, ang.cam_out.p, (size_t)P.nc * sizeof(double), hipMemcpyDeviceToHost, stream));
+        sync();
+        if (hop) {                                       // device values are in processing order; the unobserved points come last
+            for (int64_t r = 0; r < P.np; ++r) hop[P.porder[r]] = r < ang.hp1 ? tmp[r] : std::nan("");
+        }
+        for (int i = 0; i < 3; ++i) {
+            float t = 0;
+            HIPCHK(hipEventElapsedTime(&t, ang.ev[i], ang.ev[i + 1]));
+            ang.ms[i] = t;
+        }
     }
     // ---- robust reweighting (robust.hpp).  A handle that never sees a robust call has none of this: pw follows the
     // plan (uniform weights: the camera records' weights, no o_w / sg_w / cm_w).  robust_promote() gives every owned
@@ -2570,6 +2687,81 @@ int dbat_hip_redundancy(dbat_hip_handle *h, const double *x, double *qvv_ip, dou
     DeviceGuard dev_guard(c.device);
     c.x_to_z(x, c.z.p);
     c.redundancy(qvv_ip, r_prior);
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+int dbat_hip_ray_angles(dbat_hip_handle *h, const double *x, double *op_angle, double *cam_angle, int32_t *op_rays,
+                        int32_t *cam_rays) {
+    API_TRY
+    if (!h || !x) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    Core &c = *h->core;
+    if (c.P.nranks > 1) {
+        g_err = "ray angles: this handle is one shard of " + std::to_string(c.P.nranks) +
+                " (the pairs of rays across shards are not formed; use a handle of the whole problem)";
+        return DBAT_HIP_EINVAL;
+    }
+    DeviceGuard dev_guard(c.device);
+    if (op_angle || cam_angle) c.x_to_z(x, c.zt.p);
+    c.ray_angles(op_angle, cam_angle, op_rays, cam_rays);
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+/* Debug / measurement: milliseconds of the last dbat_hip_ray_angles on the handle's stream (device events): ms[0] the
+ * point kernels, ms[1] the unit directions of the images, ms[2] the pair kernel and the final acos; info[0] the
+ * v_mfma_f64_16x16x4_f64 instructions (256 pairs each) of one launch of the pair kernel, info[1] its workgroups. */
+int dbat_hip_debug_ray_angles_ms(dbat_hip_handle *h, double *ms, int64_t *info) {
+    if (!h || !ms || !info || !h->core->ang.ready) { g_err = "no ray angles computed on this handle"; return DBAT_HIP_EINVAL; }
+    for (int i = 0; i < 3; ++i) ms[i] = h->core->ang.ms[i];
+    info[0] = h->core->ang.n_mfma; info[1] = h->core->ang.n_items;
+    return DBAT_HIP_OK;
+}
+
+/* Host only, one thread: the definition of dbat_hip_ray_angles over the problem's own arrays (angles.m:26-46,
+ * camangles.m:26-46) with the arithmetic of the kernels (unit_dir, abs_dot, angle_from_min).  For tests of the
+ * definition on a machine without a GPU; never on the product path. */
+int dbat_hip_debug_ray_angles_host(const dbat_hip_problem *prob, double *op_angle, double *cam_angle) {
+    API_TRY
+    if (!prob) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    if (prob->abi_version != DBAT_HIP_ABI_VERSION) { g_err = "ABI version mismatch"; return DBAT_HIP_EINVAL; }
+    const int64_t nc = prob->n_images, np = prob->n_points, no = prob->n_obs;
+    if (nc < 0 || np < 0 || no < 0 || (no > 0 && (!prob->ip_cam || !prob->ip_pt)) || (nc > 0 && !prob->EO_val) || (np > 0 && !prob->OP_val)) {
+        g_err = "bad problem"; return DBAT_HIP_EINVAL;
+    }
+    for (int64_t o = 0; o < no; ++o)
+        if (prob->ip_cam[o] < 0 || prob->ip_cam[o] >= nc || prob->ip_pt[o] < 0 || prob->ip_pt[o] >= np) { g_err = "IP index out of range"; return DBAT_HIP_EINVAL; }
+    // side 0: the rays of every point (apex = the point, ends = camera centres); side 1: of every image
+    for (int side = 0; side < 2; ++side) {
+        double *out = side == 0 ? op_angle : cam_angle;
+        if (!out) continue;
+        const int64_t n = side == 0 ? np : nc;
+        const int32_t *own = side == 0 ? prob->ip_pt : prob->ip_cam, *other = side == 0 ? prob->ip_cam : prob->ip_pt;
+        std::vector<int64_t> start((size_t)n + 1, 0);
+        for (int64_t o = 0; o < no; ++o) ++start[(size_t)own[o] + 1];
+        for (int64_t i = 0; i < n; ++i) start[i + 1] += start[i];
+        std::vector<int32_t> lst((size_t)no);
+        {
+            std::vector<int64_t> fill(start.begin(), start.end() - 1);
+            for (int64_t o = 0; o < no; ++o) lst[(size_t)fill[own[o]]++] = other[o];
+        }
+        std::vector<double> dir;
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t k = start[i + 1] - start[i];
+            dir.resize((size_t)3 * k);
+            for (int64_t j = 0; j < k; ++j) {
+                const int32_t e = lst[(size_t)(start[i] + j)];
+                const double *q = side == 0 ? prob->OP_val + 3 * i : prob->OP_val + 3 * (int64_t)e;
+                const double *cc = side == 0 ? prob->EO_val + 6 * (int64_t)e : prob->EO_val + 6 * i;
+                unit_dir(q, cc, dir[3 * j], dir[3 * j + 1], dir[3 * j + 2]);
+            }
+            double m = INFINITY;
+            for (int64_t a = 0; a < k; ++a)
+                for (int64_t b = a + 1; b < k; ++b)
+                    m = std::fmin(m, abs_dot(dir[3 * a], dir[3 * a + 1], dir[3 * a + 2], dir[3 * b], dir[3 * b + 1], dir[3 * b + 2]));
+            out[i] = angle_from_min(k, m);
+        }
+    }
     return DBAT_HIP_OK;
     API_CATCH
 }

@@ -510,6 +510,24 @@ def bundle_reliability(s, E, alpha0=0.001, beta0=0.80, device=0):
                              omega=None if rob is None else rob.weights)
 
 
+def ray_angles(s, E=None, device=0):
+    """Ray intersection angles of the network in s, from the device (dbat_hip_ray_angles) on the handle bundle() left
+    behind -- the point angles of photogrammetry/angles.m and the image angles of photogrammetry/camangles.m at any
+    size, without the dense visibility table.  Evaluated at the values in s (E, the bundle's result struct, is accepted
+    so that the call reads like bundle_cov's; the angles depend on s.EO.val and s.OP.val alone).  Fields:
+      op        (nOP,) largest angle [rad] between two rays of every object point; 0 for one ray, NaN for none
+      cam       (nImages,) largest angle [rad] between two rays of every image; 0 for one point, NaN for none
+      op_rays   (nOP,) rays of every object point        cam_rays  (nImages,) points measured in every image"""
+    h = _hip.acquire(s, device)
+    done = False
+    try:
+        op, cam, op_rays, cam_rays = h.ray_angles(h.serialize())
+        done = True
+    finally:
+        _hip.release(h, keep=done)
+    return NS(op=op, cam=cam, op_rays=op_rays, cam_rays=cam_rays)
+
+
 def _reapply_weights(h, E):
     """A robust bundle's weight factors on an acquired handle (acquire() -> set_values restored the base weights):
     covariance and redundancy then describe the final reweighted system.  Returns E.robust."""

@@ -16,6 +16,10 @@ CIO, CEO, COP are the block-diagonal posterior covariances of bundle_cov()
 (CIO may be the full 'CIOF' matrix: then correlations between cameras are
 listed too, as the reference does).  Without them -- a failed bundle has
 none -- the report stops after the iteration summary.
+
+point_angles=(op, op_rays) (optional keyword of both; radians and ray counts as
+dbat_amd.ray_angles returns them): the "Point Angles" block is written from
+them instead of the host loop over the points and the dense visibility table.
 """
 from __future__ import annotations
 
@@ -202,7 +206,7 @@ def _angles(s, vis):
     return a
 
 
-def _quality_lines(s, E, COP, vop):
+def _quality_lines(s, E, COP, vop, point_angles=None):
     p, p2, p3, p4, p5, p6 = (_P * k for k in range(1, 7))
     out = [p + 'Quality', p2 + 'Photographs']
     ne = s.EO.val.shape[1]
@@ -317,7 +321,17 @@ def _quality_lines(s, E, COP, vop):
             if len(printed) >= 5:
                 break
     # ---- Point angles (:726-817)
-    ang = np.rad2deg(_angles(s, vis))
+    if point_angles is None:
+        ang = np.rad2deg(_angles(s, vis))
+        seen_in = lambda i: np.flatnonzero(vis[i])
+    else:
+        # precomputed (dbat_amd.ray_angles: op [rad], op_rays): this block then touches neither _angles nor the
+        # dense table -- the ray counts come with the angles, a listed point's images from the IP columns
+        ang = np.rad2deg(np.asarray(point_angles[0], float))
+        rays = np.asarray(point_angles[1]).astype(np.int64)
+        if ang.shape != (npnt,) or rays.shape != (npnt,):
+            raise ValueError('point_angles: (angles, rays) of %d object points expected' % npnt)
+        seen_in = lambda i: np.unique(np.asarray(s.IP.cam)[np.asarray(s.IP.pt) == i])
     label = getattr(s.OP, 'label', None) or [''] * npnt
     out.append(p2 + 'Point Angles')
 
@@ -355,7 +369,7 @@ def _quality_lines(s, E, COP, vop):
             # (bundle_result_file.m:809: s.IP.vis(i(j),:), i from sort(aOP)), which is the point
             # itself only when no control or check point precedes it; kept, so that the listing
             # reads as the reference's does
-            cams = ' '.join('%4d' % (c + 1) for c in np.flatnonzero(vis[order[j]]))
+            cams = ' '.join('%4d' % (c + 1) for c in seen_in(order[j]))
             out.append(p5 + '%6d: %5.2f (%s)' % (id_[order[j]], srt[j], cams))
     # ---- Control and check measurements (:819-931)
     for title, mask, delta, sep in (('Ctrl measurements', ctrl, 'Ctrl point delta', False),
@@ -402,7 +416,7 @@ def _quality_lines(s, E, COP, vop):
     return out
 
 
-def bundle_result_lines(s, E, CIO=None, CEO=None, COP=None):
+def bundle_result_lines(s, E, CIO=None, CEO=None, COP=None, point_angles=None):
     p, p2, p3, p4, p5, p6 = (_P * k for k in range(1, 7))
     have_cov = CIO is not None and CEO is not None and COP is not None
     est_io = np.asarray(s.bundle.est.IO, bool)
@@ -569,12 +583,12 @@ def bundle_result_lines(s, E, CIO=None, CEO=None, COP=None):
                 vals.append((corr_str, ','.join(' %s:%.1f%%' % (enames[pos_of[b]], v * 100) for b, v in hits) + '.'))
             out.append(p5 + nme + ':')
             out += _pretty(p6, vals, pad, pad)
-    return out + _quality_lines(s, E, COP, vop)
+    return out + _quality_lines(s, E, COP, vop, point_angles)
 
 
-def bundle_result_file(s, E, CIO=None, CEO=None, COP=None, path='report.txt'):
+def bundle_result_file(s, E, CIO=None, CEO=None, COP=None, path='report.txt', point_angles=None):
     lines = ['Damped Bundle Adjustment Toolbox result file']
-    lines += bundle_result_lines(s, E, CIO, CEO, COP)
+    lines += bundle_result_lines(s, E, CIO, CEO, COP, point_angles=point_angles)
     with open(path, 'w') as fh:
         fh.write('\n'.join(lines) + '\n')
     return lines

@@ -481,6 +481,25 @@ int  dbat_hip_posterior_cov(dbat_hip_handle *h, const double *x, double sigma0, 
  * its own observations and all ranks receive everything. */
 int  dbat_hip_redundancy(dbat_hip_handle *h, const double *x, double *qvv_ip, double *r_prior);
 
+/* Ray intersection angles at x: for every object point the largest angle between two of its rays
+ * (photogrammetry/angles.m:26-46), for every image the largest angle between two of its rays
+ * (photogrammetry/camangles.m:26-46; file/writestats.m:131, plotting/plotimagestats.m:84).  For k rays with
+ * directions d_j = Q - c_j normalised to n_j:  max over the pairs of acos(|clip(n_i . n_j, -1, 1)|), computed as
+ * acos(min_{i<j} |n_i . n_j|); exactly 0 for k = 1, NaN for k = 0.  Every IP column counts, observations of fixed
+ * and control points included.
+ *   x          the parameter vector (as for dbat_hip_posterior_cov; fixed values come from the handle)
+ *   op_angle   [n_points] radians, or NULL      cam_angle  [n_images] radians, or NULL
+ *   op_rays    [n_points] rays of every point, or NULL      cam_rays   [n_images] rays of every image, or NULL
+ *              (from the plan: no caller has to build the dense visibility table for them)
+ * The point side takes the plan's point-major order, the image side its camera-major copy with the pair products on
+ * the f64 matrix cores (csrc/angles.hpp).  Two calls give the same bits.  A handle that is one shard of several
+ * (shard_count > 1) returns DBAT_HIP_EINVAL: pairs of rays across shards are not formed. */
+int  dbat_hip_ray_angles(dbat_hip_handle *h, const double *x, double *op_angle, double *cam_angle,
+                         int32_t *op_rays, int32_t *cam_rays);
+/* Host only, one thread, no GPU: the same definition evaluated over the problem's own arrays (OP_val, EO_val, ip_cam,
+ * ip_pt), for tests of the definition; never on the product path.  Either output may be NULL. */
+int  dbat_hip_debug_ray_angles_host(const dbat_hip_problem *prob, double *op_angle, double *cam_angle);
+
 /* ---- robust estimation: iteratively reweighted least squares over the image points -------------------------------
  * For image point i (one IP column, two rows) at parameters x:
  *   s_i   = ||(w_u v_u, w_v v_v)||_2, w = 1 / (IP.std * pxSize) the BASE weights, v the unweighted residual
