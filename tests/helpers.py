@@ -339,6 +339,101 @@ def crowded_struct(kind, frac=0.85, cams=60, points=3000, control=0, selfcal=Fal
     return s, truth
 
 
+def giant_points_struct(cams, points, variant='plain'):
+    """synth.make_scene('small', rays=6) with a distortion-free camera (the projections far outside the image format
+    stay well defined) and three control points (3, 77, 250) seen in EVERY image: more observations than one batch
+    holds.  variant 'selfcal' estimates cc, px, py, K1, K2; 'selfcal-groups3' over three camera groups with IO blocks
+    of their own.  Uniform IP.std.  Returns (s, truth)."""
+    from dbat_amd import synth
+    s, truth = synth.make_scene('small', cams=cams, points=points, rays=6)
+    s.IO.val[5:10] = 0.0
+    truth['IO'][5:10] = 0.0
+    nc = s.EO.val.shape[1]
+    if variant != 'plain':
+        s.bundle.est.IO[[0, 1, 2, 5, 6]] = True
+        if variant == 'selfcal-groups3':
+            s.IO.struct.block[:] = (1 + (np.arange(nc) * 3) // nc)[None, :]
+        elif variant != 'selfcal':
+            raise ValueError(variant)
+    px = float(np.ravel(s.IO.sensor.pxSize)[0])
+    rng = np.random.default_rng(5)
+    add_cam, add_pt = [], []
+    for p in (3, 77, 250):
+        have = set(s.IP.cam[s.IP.pt == p].tolist())
+        for c in range(nc):
+            if c not in have:
+                add_cam.append(c); add_pt.append(p)
+    cam = np.r_[s.IP.cam, np.array(add_cam)]; pt = np.r_[s.IP.pt, np.array(add_pt)]
+    order = np.lexsort((pt, cam))                       # image-major, ascending OP
+    cam, pt = cam[order], pt[order]
+    uv, depth = synth.project(truth['IO'], truth['EO'], truth['OP'], cam, pt, px, nK=3, nP=2)
+    assert np.all(depth < 0)
+    s.IP.val = uv + rng.normal(0, 0.5, uv.shape)
+    s.IP.std = np.ones_like(uv)
+    s.IP.cam, s.IP.pt = cam, pt
+    assert np.bincount(s.IP.pt).max() == nc
+    return s, truth
+
+
+def mixed_heavy_struct(variant):
+    """synth 'small' with every second point thinned out to 4 rays: with DBAT_HIP_CMAX=6 the 8-ray points are heavy,
+    next to tiled points in one problem.  Returns (s, truth)."""
+    s, truth = synth_struct('small', variant)
+    pt, cam = s.IP.pt, s.IP.cam
+    rank = np.zeros(len(pt), int)
+    order = np.lexsort((cam, pt))
+    first = np.r_[True, pt[order][1:] != pt[order][:-1]]
+    idx = np.arange(len(pt)) - np.maximum.accumulate(np.where(first, np.arange(len(pt)), 0))
+    rank[order] = idx
+    keep = ~((pt % 2 == 0) & (rank >= 4))
+    s.IP.val, s.IP.std = s.IP.val[:, keep], s.IP.std[:, keep]
+    s.IP.cam, s.IP.pt = s.IP.cam[keep], s.IP.pt[keep]
+    return s, truth
+
+
+def all_see_all_scene(cams, points, selfcal, groups=1, seed=3):
+    """Every point in every image (the geometry of the reference's calibration demo, demo/camcaldemo.m:56-119)."""
+    from dbat_amd import synth
+    return synth.make_dense_scene(cams, points, selfcal, groups, seed)
+
+
+# ---------------------------------------------------------------- per-observation weight factors (tests/test_obs_weights_*.py)
+def obs_weight_factors(no, seed, lo=1e-2):
+    """Weight factors omega in [lo, 1] of `no` image points: log-uniform, about 10 % exactly 1.0 and about 1 % exactly
+    lo -- a spread wide enough that a weight on the wrong observation moves the step far above any tolerance."""
+    rng = np.random.default_rng(seed)
+    om = np.exp(rng.uniform(np.log(lo), 0.0, no))
+    u = rng.random(no)
+    om[u < 0.10] = 1.0
+    om[(u >= 0.10) & (u < 0.11)] = lo
+    return np.minimum(om, 1.0)
+
+
+def std_pattern(s):
+    """A copy of s with the non-uniform IP.std of synth_struct's 'priors' variant: IP.std * (1 + 0.5 * (i % 3))."""
+    import copy
+    t = copy.deepcopy(s)
+    t.IP.std = np.asfortranarray(np.asarray(t.IP.std, float) * (1 + (np.arange(t.IP.std.shape[1]) % 3)[None, :] * 0.5))
+    t.IP.sigmas = np.unique(t.IP.std)
+    return t
+
+
+def reweighted_struct(s, omega):
+    """The same least-squares problem as s with the weight factor omega_i on image point i: IP.std[:, i] / sqrt(omega_i)."""
+    import copy
+    t = copy.deepcopy(s)
+    t.IP.std = np.asfortranarray(np.asarray(t.IP.std, float) / np.sqrt(np.asarray(omega, float))[None, :])
+    t.IP.sigmas = np.unique(t.IP.std)
+    return t
+
+
+def base_image_weights(s):
+    """(nObs, 2) base weights 1 / (IP.std * pxSize) of the image rows, in the row order of the residual vector."""
+    px = np.asarray(s.IO.sensor.pxSize, float)
+    px = px[:, s.IP.cam] if px.shape[1] > 1 else px
+    return (1.0 / (np.asarray(s.IP.std, float) * px)).T
+
+
 def relerr(a, b):
     """misc/relerr.m: Frobenius relative error."""
     a, b = np.asarray(a, float), np.asarray(b, float)

@@ -17,7 +17,8 @@ import scipy.sparse as sp
 
 import dbat_oracle as o
 from helpers import (camcal_struct, camcal_expected, check_camcal_against_report, synth_struct,
-                     relerr, roma_struct, roma_expected, check_roma_against_result, lm_count_is_stable)
+                     relerr, roma_struct, roma_expected, check_roma_against_result, lm_count_is_stable,
+                     all_see_all_scene as _all_see_all_scene, giant_points_struct, mixed_heavy_struct)
 
 pytestmark = pytest.mark.gpu
 
@@ -797,17 +798,8 @@ def test_mixed_tiled_and_heavy_points(hip, variant, monkeypatch):
     next to tiled points (MFMA kernel) in one problem: step parity with the
     oracle and an identical bundle result."""
     from dbat_amd import bundle
-    s, truth = synth_struct('small', variant)
-    # thin out every second point to 4 rays; with CMAX=6 the 8-ray points are heavy
-    pt, cam = s.IP.pt, s.IP.cam
-    rank = np.zeros(len(pt), int)
-    order = np.lexsort((cam, pt))
-    first = np.r_[True, pt[order][1:] != pt[order][:-1]]
-    idx = np.arange(len(pt)) - np.maximum.accumulate(np.where(first, np.arange(len(pt)), 0))
-    rank[order] = idx
-    keep = ~((pt % 2 == 0) & (rank >= 4))
-    s.IP.val, s.IP.std = s.IP.val[:, keep], s.IP.std[:, keep]
-    s.IP.cam, s.IP.pt = s.IP.cam[keep], s.IP.pt[keep]
+    # every second point thinned out to 4 rays; with CMAX=6 the 8-ray points are heavy
+    s, truth = mixed_heavy_struct(variant)
     monkeypatch.setenv('DBAT_HIP_CMAX', '6')
     so, x0, w = oracle_setup(s)
     R = np.sqrt(w)
@@ -839,29 +831,9 @@ def test_giant_points(hip, variant, monkeypatch):
     k_build_giant / k_backsub_giant: step parity with the oracle and an
     identical bundle result.  Distortion-free camera, so that the projections
     far outside the image format stay well defined."""
-    from dbat_amd import bundle, synth
-    s, truth = synth.make_scene('small', cams=140, points=500, rays=6)
-    s.IO.val[5:10] = 0.0
-    truth['IO'][5:10] = 0.0
-    if variant == 'selfcal':
-        s.bundle.est.IO[[0, 1, 2, 5, 6]] = True
+    from dbat_amd import bundle
+    s, truth = giant_points_struct(140, 500, variant)
     nc = s.EO.val.shape[1]
-    px = float(np.ravel(s.IO.sensor.pxSize)[0])
-    rng = np.random.default_rng(5)
-    add_cam, add_pt = [], []
-    for p in (3, 77, 250):
-        have = set(s.IP.cam[s.IP.pt == p].tolist())
-        for c in range(nc):
-            if c not in have:
-                add_cam.append(c); add_pt.append(p)
-    cam = np.r_[s.IP.cam, np.array(add_cam)]; pt = np.r_[s.IP.pt, np.array(add_pt)]
-    order = np.lexsort((pt, cam))                       # image-major, ascending OP
-    cam, pt = cam[order], pt[order]
-    uv, depth = synth.project(truth['IO'], truth['EO'], truth['OP'], cam, pt, px, nK=3, nP=2)
-    assert np.all(depth < 0)
-    s.IP.val = uv + rng.normal(0, 0.5, uv.shape)
-    s.IP.std = np.ones_like(uv)
-    s.IP.cam, s.IP.pt = cam, pt
     assert np.bincount(s.IP.pt).max() == nc
     monkeypatch.setenv('DBAT_HIP_BT', '128')
     monkeypatch.setenv('DBAT_HIP_GIANT_THREADS', '64')
@@ -885,42 +857,13 @@ def test_giant_points(hip, variant, monkeypatch):
     assert ok and oko and iters == ito and relerr(E.x, Eo.x) < TOL_X
 
 
-def _all_see_all_scene(cams, points, selfcal, groups=1, seed=3):
-    """Every point in every image (the geometry of the reference's calibration demo, demo/camcaldemo.m:56-119)."""
-    from dbat_amd import synth
-    return synth.make_dense_scene(cams, points, selfcal, groups, seed)
-
-
 @pytest.mark.parametrize('variant', ['plain', 'selfcal', 'selfcal-groups3'])
 def test_giant_points_on_the_matrix_cores(hip, variant, monkeypatch):
     """csrc/heavy.hpp: points seen in all 300 images (more than a 256-observation batch holds: k_heavy_z_giant, three
     rounds of 128 threads) beside ordinary tiled points, their Schur terms by k_heavy_syrk over 38 camera groups.  Step,
     ||J p||^2 and gradient against the oracle, the bundle against the oracle's, the deterministic mode bit for bit."""
-    from dbat_amd import bundle, synth
-    s, truth = synth.make_scene('small', cams=300, points=400, rays=6)
-    s.IO.val[5:10] = 0.0
-    truth['IO'][5:10] = 0.0
-    nc = s.EO.val.shape[1]
-    if variant != 'plain':
-        s.bundle.est.IO[[0, 1, 2, 5, 6]] = True
-        if variant == 'selfcal-groups3':
-            s.IO.struct.block[:] = (1 + (np.arange(nc) * 3) // nc)[None, :]
-    px = float(np.ravel(s.IO.sensor.pxSize)[0])
-    rng = np.random.default_rng(5)
-    add_cam, add_pt = [], []
-    for p in (3, 77, 250):
-        have = set(s.IP.cam[s.IP.pt == p].tolist())
-        for c in range(nc):
-            if c not in have:
-                add_cam.append(c); add_pt.append(p)
-    cam = np.r_[s.IP.cam, np.array(add_cam)]; pt = np.r_[s.IP.pt, np.array(add_pt)]
-    order = np.lexsort((pt, cam))
-    cam, pt = cam[order], pt[order]
-    uv, depth = synth.project(truth['IO'], truth['EO'], truth['OP'], cam, pt, px, nK=3, nP=2)
-    assert np.all(depth < 0)
-    s.IP.val = uv + rng.normal(0, 0.5, uv.shape)
-    s.IP.std = np.ones_like(uv)
-    s.IP.cam, s.IP.pt = cam, pt
+    from dbat_amd import bundle
+    s, truth = giant_points_struct(300, 400, variant)
     monkeypatch.setenv('DBAT_HIP_GIANT_THREADS', '128')
     so, x0, w = oracle_setup(s)
     R = np.sqrt(w)

@@ -7,7 +7,7 @@ import pytest
 import scipy.sparse as sp
 
 import dbat_oracle as o
-from helpers import camcal_struct, roma_struct, sxb_prior_eo_struct, synth_struct
+from helpers import camcal_struct, giant_points_struct, roma_struct, sxb_prior_eo_struct, synth_struct
 from test_reliability_cpu import _oracle_setup, dense_reliability
 
 pytestmark = pytest.mark.gpu
@@ -96,27 +96,7 @@ def test_sampled_at_size_C1(hip):
 
 def _giant_scene():
     """test_giant_points' scene: three control points seen in all 140 images (more than a 128-observation batch)."""
-    from dbat_amd import synth
-    s, truth = synth.make_scene('small', cams=140, points=500, rays=6)
-    s.IO.val[5:10] = 0.0
-    truth['IO'][5:10] = 0.0
-    s.bundle.est.IO[[0, 1, 2, 5, 6]] = True
-    nc = s.EO.val.shape[1]
-    px = float(np.ravel(s.IO.sensor.pxSize)[0])
-    add_cam, add_pt = [], []
-    for p in (3, 77, 250):
-        have = set(s.IP.cam[s.IP.pt == p].tolist())
-        for c in range(nc):
-            if c not in have:
-                add_cam.append(c); add_pt.append(p)
-    cam = np.r_[s.IP.cam, np.array(add_cam)]; pt = np.r_[s.IP.pt, np.array(add_pt)]
-    order = np.lexsort((pt, cam))
-    cam, pt = cam[order], pt[order]
-    uv, _ = synth.project(truth['IO'], truth['EO'], truth['OP'], cam, pt, px, nK=3, nP=2)
-    s.IP.val = uv + np.random.default_rng(5).normal(0, 0.5, uv.shape)
-    s.IP.std = np.ones_like(uv)
-    s.IP.cam, s.IP.pt = cam, pt
-    return s
+    return giant_points_struct(140, 500, 'selfcal')[0]
 
 
 def test_routes_agree(hip, monkeypatch):
