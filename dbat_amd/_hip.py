@@ -42,6 +42,7 @@ class DbatHipError(RuntimeError):
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_lp = C.POINTER(C.c_int64)
 _bp = C.POINTER(C.c_uint8)
 
 
@@ -175,6 +176,10 @@ SYMBOLS = {
     'dbat_hip_redundancy': (C.c_int, [_H, _dp, _dp, _dp]),
     'dbat_hip_ray_angles': (C.c_int, [_H, _dp, _dp, _dp, _ip, _ip]),
     'dbat_hip_debug_ray_angles_host': (C.c_int, [C.POINTER(Problem), _dp, _dp]),
+    'dbat_hip_coverage': (C.c_int, [_H, _dp, _dp, _dp, _lp, _dp, _lp, _lp]),
+    'dbat_hip_residual_stats': (C.c_int, [_H, _dp, _lp, _dp, _lp, _dp, _dp, _dp, _lp]),
+    'dbat_hip_quality_hull_cap': (C.c_int32, []),
+    'dbat_hip_debug_coverage_host': (C.c_int, [C.POINTER(Problem), _dp, _dp, _dp, _lp, _dp, _lp, _lp]),
     'dbat_hip_default_robust_options': (C.c_int, [C.c_int32, C.POINTER(RobustOptions)]),
     'dbat_hip_robust_weights': (C.c_int, [_H, _dp, C.POINTER(RobustOptions), _dp, _dp, _dp]),
     'dbat_hip_set_obs_weights': (C.c_int, [_H, _dp]),
@@ -188,6 +193,7 @@ DEBUG_SYMBOLS = {
     'dbat_hip_debug_model_eval_host': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_double,
                                                  _dp, _dp, _dp, _dp, _dp, _dp]),
     'dbat_hip_debug_ray_angles_ms': (C.c_int, [_H, _dp, C.POINTER(C.c_int64)]),
+    'dbat_hip_debug_quality_ms': (C.c_int, [_H, _dp]),
 }
 
 _lib = None
@@ -627,6 +633,33 @@ class Handle:
         return dict(points=float(ms[0]), cam_dirs=float(ms[1]), cam_pairs=float(ms[2]), mfma=int(info[0]),
                     workgroups=int(info[1]))
 
+    def coverage(self):
+        """Image coverage by the measured points (dbat_hip_coverage), per image: a dict with lo, hi (2, nImages), rad_max
+        [mm], rad_ip, hull_area [px^2] and hull, the list of the hulls' vertices as arrays of IP columns
+        (counter-clockwise from the lowest (u, v), closing point not repeated).  DbatHipError on a sharded handle."""
+        return _coverage_call(lambda *a: self.lib.dbat_hip_coverage(self.h, *a), int(self.prob.n_images), int(self.prob.n_obs))
+
+    def residual_stats(self, x):
+        """Marking-residual statistics at x (dbat_hip_residual_stats): a dict with cam_n, cam_ss (per image), op_n, op_ss
+        (per object point), total_ss, max_e and max_ip -- sums of squared pixel residual norms, the largest norm and
+        its IP column."""
+        x = np.ascontiguousarray(x, float)
+        nc, npnt = int(self.prob.n_images), int(self.prob.n_points)
+        cam_n, op_n = np.zeros(max(nc, 1), np.int64), np.zeros(max(npnt, 1), np.int64)
+        cam_ss, op_ss = np.zeros(max(nc, 1)), np.zeros(max(npnt, 1))
+        tot, mx, mip = C.c_double(), C.c_double(), C.c_int64()
+        check(self.lib.dbat_hip_residual_stats(self.h, dptr(x), cam_n.ctypes.data_as(_lp), dptr(cam_ss),
+                                               op_n.ctypes.data_as(_lp), dptr(op_ss), C.cast(C.byref(tot), _dp),
+                                               C.cast(C.byref(mx), _dp), C.cast(C.byref(mip), _lp)))
+        return dict(cam_n=cam_n[:nc], cam_ss=cam_ss[:nc], op_n=op_n[:npnt], op_ss=op_ss[:npnt], total_ss=tot.value,
+                    max_e=mx.value, max_ip=int(mip.value))
+
+    def quality_ms(self):
+        """Device-event milliseconds of the kernels of the last coverage() and the last residual_stats() (debug)."""
+        ms = np.zeros(2)
+        check(self.lib.dbat_hip_debug_quality_ms(self.h, dptr(ms)))
+        return dict(coverage=float(ms[0]), residual_stats=float(ms[1]))
+
     def robust_weights(self, x, ropt):
         """One reweighting evaluation at x, not applied (dbat_hip_robust_weights): (omega, s_norm, scale), the two
         vectors per IP column."""
@@ -891,6 +924,29 @@ def debug_model_eval_host(model, nK, nP, EO6, IO, px, Q, uv):
     check(lib.dbat_hip_debug_model_eval_host(model, nK, nP, dptr(a[0]), dptr(a[1]), float(px),
                                              dptr(a[2]), dptr(a[3]), dptr(r), dptr(A), dptr(B), dptr(Cc)))
     return r, A.reshape(6, 2).T, B.reshape(3, 2).T, Cc.reshape(R, 2).T
+
+
+def _coverage_call(fn, nc, no):
+    lo, hi = np.zeros(2 * max(nc, 1)), np.zeros(2 * max(nc, 1))
+    rad, area = np.zeros(max(nc, 1)), np.zeros(max(nc, 1))
+    rip, hs, hip = np.zeros(max(nc, 1), np.int64), np.zeros(nc + 1, np.int64), np.zeros(max(no, 1), np.int64)
+    lp = lambda a: a.ctypes.data_as(_lp)
+    check(fn(dptr(lo), dptr(hi), dptr(rad), lp(rip), dptr(area), lp(hs), lp(hip)))
+    return dict(lo=lo[:2 * nc].reshape(2, nc, order='F'), hi=hi[:2 * nc].reshape(2, nc, order='F'), rad_max=rad[:nc],
+                rad_ip=rip[:nc], hull_area=area[:nc], hull=[hip[hs[c]:hs[c + 1]].copy() for c in range(nc)])
+
+
+def quality_hull_cap():
+    """Candidates of one image that the coverage kernel sorts in LDS (QUAL_HULL_CAP)."""
+    return int(load().dbat_hip_quality_hull_cap())
+
+
+def debug_coverage_host(s):
+    """Host evaluation of dbat_hip_coverage over the struct's own values with the kernel's code (no GPU needed): the
+    dict of Handle.coverage()."""
+    lib = load()
+    p, keep = problem_from_struct(s)
+    return _coverage_call(lambda *a: lib.dbat_hip_debug_coverage_host(C.byref(p), *a), int(p.n_images), int(p.n_obs))
 
 
 def debug_ray_angles_host(s):

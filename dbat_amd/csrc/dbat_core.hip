@@ -26,6 +26,7 @@
 #include "resect.hpp"
 #include "robust.hpp"
 #include "angles.hpp"
+#include "quality.hpp"
 
 namespace dbat {
 
@@ -1348,6 +1349,135 @@ struct Core {
             HIPCHK(hipEventElapsedTime(&t, ang.ev[i], ang.ev[i + 1]));
             ang.ms[i] = t;
         }
+    }
+    // ---- image coverage and marking-residual statistics (quality.hpp).  Built by the first call and kept, as the
+    // angles' plan: the columns of every image (IP is image-major), where every point's observations start, the
+    // measured pixel coordinates in IP order (the observations are structure: dbat_hip_set_values never changes them;
+    // the principal point is read from io_fixed, which it does change), the index scratch of the images with more
+    // than QUAL_HULL_CAP points.
+    struct QualPlan {
+        bool ready = false;
+        int32_t hp0 = 0, hp1 = 0;                        // heavy / giant points: [hp0, hp1) of the processing order
+        std::vector<int64_t> ip_start;                   // [nc + 1]
+        std::vector<int64_t> op_n;                       // per point (caller's order)
+        DevBuf<int64_t> d_ip_start, pt_pos, big_off, rad_ip, hull_start, hull_ip, cam_max_ip, max_ip;
+        DevBuf<int32_t> big_idx, hull_tmp, hull_n;
+        DevBuf<double> ip_uv, lo, hi, rad_max, hull_area, r, e2, cam_ss, cam_max, op_ss, tot;
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+        double ms[2] = {0, 0};                           // last dbat_hip_coverage, last dbat_hip_residual_stats (kernels only)
+        ~QualPlan() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+    } qual;
+    void qual_plan() {
+        if (qual.ready) return;
+        const int64_t npt = P.np, no = nobs;
+        const int nc = P.nc;
+        qual.ip_start.assign((size_t)nc + 1, 0);
+        for (int64_t o = 0; o < no; ++o) ++qual.ip_start[(size_t)P.o_cam[o] + 1];
+        for (int c = 0; c < nc; ++c) qual.ip_start[(size_t)c + 1] += qual.ip_start[c];
+        std::vector<int64_t> pos((size_t)npt + 1, 0);
+        for (int64_t o = 0; o < no; ++o) {
+            const int c = P.o_cam[o];
+            if (P.o_row[o] < qual.ip_start[c] || P.o_row[o] >= qual.ip_start[(size_t)c + 1])
+                throw UsageError{"network quality: the image points are not image-major (the columns of an image must be contiguous, images ascending)"};
+            ++pos[(size_t)P.o_pt[o] + 1];
+        }
+        qual.op_n.assign((size_t)npt, 0);
+        for (int64_t r = 0; r < npt; ++r) qual.op_n[P.porder[r]] = pos[r + 1];
+        for (int64_t r = 0; r < npt; ++r) pos[r + 1] += pos[r];
+        const int64_t ho0 = P.batch_start[std::min<int64_t>(P.nb_tiled, nb)];
+        qual.hp1 = no > 0 ? P.o_pt[no - 1] + 1 : 0;
+        qual.hp0 = ho0 < no ? P.o_pt[ho0] : qual.hp1;
+        std::vector<int64_t> boff((size_t)nc, 0);
+        int64_t nbig = 0;
+        for (int c = 0; c < nc; ++c) {
+            const int64_t n = qual.ip_start[(size_t)c + 1] - qual.ip_start[c];
+            if (n >= ((int64_t)1 << 30)) throw UsageError{"network quality: an image with more than 2^30 points"};
+            boff[c] = nbig;
+            if (n > QUAL_HULL_CAP) { int64_t m2 = 1; while (m2 < n) m2 <<= 1; nbig += m2; }
+        }
+        qual.d_ip_start.upload(qual.ip_start); qual.pt_pos.upload(pos); qual.big_off.upload(boff);
+        qual.big_idx.alloc((size_t)std::max<int64_t>(nbig, 1));
+        const size_t nc1 = (size_t)std::max(nc, 1), no1 = (size_t)std::max<int64_t>(no, 1);
+        qual.ip_uv.alloc(2 * no1);
+        qual.hull_tmp.alloc(no1 + nc1); qual.hull_n.alloc(nc1); qual.hull_start.alloc(nc1 + 1); qual.hull_ip.alloc(no1);
+        qual.lo.alloc(2 * nc1); qual.hi.alloc(2 * nc1); qual.rad_max.alloc(nc1); qual.rad_ip.alloc(nc1); qual.hull_area.alloc(nc1);
+        qual.r.alloc(2 * no1); qual.e2.alloc(no1); qual.cam_ss.alloc(nc1); qual.cam_max.alloc(nc1); qual.cam_max_ip.alloc(nc1);
+        qual.op_ss.alloc((size_t)std::max<int64_t>(npt, 1)); qual.tot.alloc(2); qual.max_ip.alloc(1);
+        if (no > 0) launch<k_qual_ip_uv>(dim3((unsigned)cdiv(no, 256)), dim3(256), 0, no, o_row.p, o_uv.p, qual.ip_uv.p);
+        for (auto &e : qual.ev) HIPCHK(hipEventCreate(&e));
+        qual.ready = true;
+    }
+    static constexpr size_t qual_hull_lds = ((size_t)QUAL_HULL_CAP * 20 + ((size_t)QUAL_HULL_CAP + 1) * 4 + 7) / 8 * 8;
+    void coverage(double *hlo, double *hhi, double *hrad, int64_t *hrad_ip, double *harea, int64_t *hstart, int64_t *hip_) {
+        qual_plan();
+        const int nc = P.nc;
+        HIPCHK(hipEventRecord(qual.ev[0], stream));
+        if (nc > 0)
+            launch<k_qual_hull>(dim3((unsigned)nc), dim3(QUAL_THREADS), qual_hull_lds, qual.d_ip_start.p, qual.ip_uv.p, px.p, io_fixed.p, P.nIOrows,
+                                qual.big_idx.p, qual.big_off.p, qual.lo.p, qual.hi.p, qual.rad_max.p, qual.rad_ip.p, qual.hull_area.p,
+                                qual.hull_tmp.p, qual.hull_n.p);
+        HIPCHK(hipEventRecord(qual.ev[1], stream));
+        if (hlo) HIPCHK(hipMemcpyAsync(hlo, qual.lo.p, (size_t)2 * nc * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (hhi) HIPCHK(hipMemcpyAsync(hhi, qual.hi.p, (size_t)2 * nc * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (hrad) HIPCHK(hipMemcpyAsync(hrad, qual.rad_max.p, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (hrad_ip) HIPCHK(hipMemcpyAsync(hrad_ip, qual.rad_ip.p, (size_t)nc * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+        if (harea) HIPCHK(hipMemcpyAsync(harea, qual.hull_area.p, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, stream));
+        std::vector<int32_t> hn((size_t)nc);
+        std::vector<int64_t> hs((size_t)nc + 1, 0);
+        if (hstart || hip_) HIPCHK(hipMemcpyAsync(hn.data(), qual.hull_n.p, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        sync();
+        float t = 0;
+        HIPCHK(hipEventElapsedTime(&t, qual.ev[0], qual.ev[1]));
+        qual.ms[0] = t;
+        if (!hstart && !hip_) return;
+        for (int c = 0; c < nc; ++c) hs[(size_t)c + 1] = hs[c] + hn[c];
+        if (hstart) std::copy(hs.begin(), hs.end(), hstart);
+        if (!hip_ || hs[nc] == 0) return;
+        HIPCHK(hipMemcpyAsync(qual.hull_start.p, hs.data(), ((size_t)nc + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+        launch<k_qual_hull_pack>(dim3((unsigned)nc), dim3(256), 0, qual.d_ip_start.p, qual.hull_tmp.p, qual.hull_start.p, qual.hull_ip.p);
+        HIPCHK(hipMemcpyAsync(hip_, qual.hull_ip.p, (size_t)hs[nc] * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+        sync();
+    }
+    // at zt
+    void residual_stats(int64_t *hcam_n, double *hcam_ss, int64_t *hop_n, double *hop_ss, double *htot, double *hmax, int64_t *hmax_ip) {
+        qual_plan();
+        const int nc = P.nc;
+        if (hcam_n) for (int c = 0; c < nc; ++c) hcam_n[c] = qual.ip_start[(size_t)c + 1] - qual.ip_start[c];
+        if (hop_n) std::copy(qual.op_n.begin(), qual.op_n.end(), hop_n);
+        if (!hcam_ss && !hop_ss && !htot && !hmax && !hmax_ip) return;
+        const double *zz = zt.p;
+        prep_cams(zz, cams_f.p);
+        HIPCHK(hipEventRecord(qual.ev[0], stream));
+        if (nobs > 0)
+            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(uv_pre, [&](auto PRE) {
+                launch<k_residual<M, PRE>>(dim3(grid_obs), dim3(256), 0, d, zz, cams_f.p, rpart.p, (double *)nullptr, qual.r.p);
+            }); });
+        if (nc > 0)
+            launch<k_qual_cam_res>(dim3((unsigned)nc), dim3(256), 0, qual.d_ip_start.p, qual.r.p, px.p, qual.e2.p, qual.cam_ss.p, qual.cam_max.p, qual.cam_max_ip.p);
+        if (hop_ss) {
+            if (qual.hp0 > 0) launch<k_qual_pt_light>(dim3((unsigned)cdiv(qual.hp0, 256)), dim3(256), 0, qual.pt_pos.p, o_row.p, qual.e2.p, qual.hp0, qual.op_ss.p);
+            if (qual.hp1 > qual.hp0) launch<k_qual_pt_heavy>(dim3((unsigned)(qual.hp1 - qual.hp0)), dim3(64), 0, qual.pt_pos.p, o_row.p, qual.e2.p, qual.hp0, qual.op_ss.p);
+        }
+        launch<k_qual_total>(dim3(1), dim3(256), 0, nc, qual.cam_ss.p, qual.cam_max.p, qual.cam_max_ip.p, qual.tot.p, qual.max_ip.p);
+        HIPCHK(hipEventRecord(qual.ev[1], stream));
+        std::vector<double> tmp;
+        double tot[2] = {0, 0};
+        int64_t mip = -1;
+        if (hcam_ss) HIPCHK(hipMemcpyAsync(hcam_ss, qual.cam_ss.p, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (hop_ss && qual.hp1 > 0) {
+            tmp.resize((size_t)qual.hp1);
+            HIPCHK(hipMemcpyAsync(tmp.data(), qual.op_ss.p, (size_t)qual.hp1 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        }
+        HIPCHK(hipMemcpyAsync(tot, qual.tot.p, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(&mip, qual.max_ip.p, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+        sync();
+        if (hop_ss) for (int64_t r = 0; r < P.np; ++r) hop_ss[P.porder[r]] = r < qual.hp1 ? tmp[r] : 0.0;   // (the unobserved points come last)
+        if (htot) *htot = tot[0];
+        if (hmax) *hmax = tot[1];
+        if (hmax_ip) *hmax_ip = mip;
+        float t = 0;
+        HIPCHK(hipEventElapsedTime(&t, qual.ev[0], qual.ev[1]));
+        qual.ms[1] = t;
     }
     // ---- robust reweighting (robust.hpp).  A handle that never sees a robust call has none of this: pw follows the
     // plan (uniform weights: the camera records' weights, no o_w / sg_w / cm_w).  robust_promote() gives every owned
@@ -2761,6 +2891,123 @@ int dbat_hip_debug_ray_angles_host(const dbat_hip_problem *prob, double *op_angl
                     m = std::fmin(m, abs_dot(dir[3 * a], dir[3 * a + 1], dir[3 * a + 2], dir[3 * b], dir[3 * b + 1], dir[3 * b + 2]));
             out[i] = angle_from_min(k, m);
         }
+    }
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+static bool quality_one_rank(const Core &c, const char *what) {
+    if (c.P.nranks <= 1) return true;
+    g_err = std::string(what) + ": this handle is one shard of " + std::to_string(c.P.nranks) +
+            " (an image's points are spread over the shards; use a handle of the whole problem)";
+    return false;
+}
+
+int dbat_hip_coverage(dbat_hip_handle *h, double *lo, double *hi, double *rad_max, int64_t *rad_ip, double *hull_area,
+                      int64_t *hull_start, int64_t *hull_ip) {
+    API_TRY
+    if (!h) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    Core &c = *h->core;
+    if (!quality_one_rank(c, "coverage")) return DBAT_HIP_EINVAL;
+    DeviceGuard dev_guard(c.device);
+    c.coverage(lo, hi, rad_max, rad_ip, hull_area, hull_start, hull_ip);
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+int dbat_hip_residual_stats(dbat_hip_handle *h, const double *x, int64_t *cam_n, double *cam_ss, int64_t *op_n, double *op_ss,
+                            double *total_ss, double *max_e, int64_t *max_ip) {
+    API_TRY
+    if (!h || !x) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    Core &c = *h->core;
+    if (!quality_one_rank(c, "residual statistics")) return DBAT_HIP_EINVAL;
+    DeviceGuard dev_guard(c.device);
+    if (cam_ss || op_ss || total_ss || max_e || max_ip) c.x_to_z(x, c.zt.p);
+    c.residual_stats(cam_n, cam_ss, op_n, op_ss, total_ss, max_e, max_ip);
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+int32_t dbat_hip_quality_hull_cap(void) { return QUAL_HULL_CAP; }
+
+/* Debug / measurement: milliseconds of the kernels of the last dbat_hip_coverage (ms[0]) and of the last
+ * dbat_hip_residual_stats (ms[1], the residual pass included) on the handle's stream (device events). */
+int dbat_hip_debug_quality_ms(dbat_hip_handle *h, double *ms) {
+    if (!h || !ms || !h->core->qual.ready) { g_err = "no coverage or residual statistics computed on this handle"; return DBAT_HIP_EINVAL; }
+    ms[0] = h->core->qual.ms[0]; ms[1] = h->core->qual.ms[1];
+    return DBAT_HIP_OK;
+}
+
+/* Host only, one thread: dbat_hip_coverage over the problem's own arrays with the code of the kernel (octagon filter,
+ * order, chain scan, shoelace sum of quality.hpp; std::sort in place of the network).  For tests on a machine without
+ * a GPU; never on the product path. */
+int dbat_hip_debug_coverage_host(const dbat_hip_problem *prob, double *lo, double *hi, double *rad_max, int64_t *rad_ip,
+                                 double *hull_area, int64_t *hull_start, int64_t *hull_ip) {
+    API_TRY
+    if (!prob) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    if (prob->abi_version != DBAT_HIP_ABI_VERSION) { g_err = "ABI version mismatch"; return DBAT_HIP_EINVAL; }
+    const int64_t nc = prob->n_images, no = prob->n_obs;
+    if (nc < 0 || no < 0 || (no > 0 && (!prob->ip_cam || !prob->ip_val)) || (nc > 0 && (!prob->IO_val || !prob->px_size))) {
+        g_err = "bad problem"; return DBAT_HIP_EINVAL;
+    }
+    const int R = 5 + prob->nK + prob->nP;
+    std::vector<int64_t> start((size_t)nc + 1, 0);
+    for (int64_t o = 0; o < no; ++o) {
+        if (prob->ip_cam[o] < 0 || prob->ip_cam[o] >= nc || (o > 0 && prob->ip_cam[o] < prob->ip_cam[o - 1])) {
+            g_err = "IP.cam out of range or not image-major"; return DBAT_HIP_EINVAL;
+        }
+        ++start[(size_t)prob->ip_cam[o] + 1];
+    }
+    for (int64_t c = 0; c < nc; ++c) start[c + 1] += start[c];
+    const double nan = std::nan("");
+    std::vector<int32_t> idx, stk;
+    int64_t nh = 0;
+    if (hull_start) hull_start[0] = 0;
+    for (int64_t c = 0; c < nc; ++c) {
+        const int64_t i0 = start[c];
+        const int n = (int)(start[c + 1] - i0);
+        const double *uv = prob->ip_val + 2 * i0;
+        double l[2] = {nan, nan}, hh[2] = {nan, nan}, rm = nan, area = 0.0;
+        int64_t ri = -1;
+        int h = 0;
+        if (n > 0) {
+            double ev[9];
+            int ei[9];
+            for (int k = 0; k < 9; ++k) { ev[k] = -INFINITY; ei[k] = -1; }
+            for (int i = 0; i < n; ++i)
+                for (int k = 0; k < 9; ++k) {
+                    const double f = k < 8 ? qual_dir(k, uv[2 * i], uv[2 * i + 1])
+                                           : qual_radius(uv[2 * i], uv[2 * i + 1], prob->px_size[2 * c], prob->px_size[2 * c + 1],
+                                                         prob->IO_val[c * R + 1], prob->IO_val[c * R + 2]);
+                    if (ei[k] < 0 || f > ev[k]) { ev[k] = f; ei[k] = i; }
+                }
+            double eu[8], evv[8];
+            for (int k = 0; k < 8; ++k) { eu[k] = uv[2 * ei[k]]; evv[k] = uv[2 * ei[k] + 1]; }
+            l[0] = eu[0]; hh[0] = eu[4]; l[1] = evv[2]; hh[1] = evv[6];
+            rm = ev[8]; ri = i0 + ei[8];
+            QualOct oct;
+            qual_oct_build(eu, evv, hh[0] - l[0], hh[1] - l[1], oct);
+            idx.clear();
+            for (int i = 0; i < n; ++i) if (!qual_oct_inside(oct, uv[2 * i], uv[2 * i + 1])) idx.push_back(i);
+            const int ns = (int)idx.size();
+            const QualIdxPts p{uv, idx.data()};
+            std::sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) {        // the order of qual_less
+                if (uv[2 * a] != uv[2 * b]) return uv[2 * a] < uv[2 * b];
+                if (uv[2 * a + 1] != uv[2 * b + 1]) return uv[2 * a + 1] < uv[2 * b + 1];
+                return a < b;
+            });
+            stk.assign((size_t)ns + 1, 0);
+            h = qual_hull_chain(p, ns, stk.data());
+            area = qual_hull_area(p, stk.data(), h, l[0], l[1]);
+            if (hull_ip) for (int j = 0; j < h; ++j) hull_ip[nh + j] = i0 + idx[stk[j]];
+        }
+        nh += h;
+        if (lo) { lo[2 * c] = l[0]; lo[2 * c + 1] = l[1]; }
+        if (hi) { hi[2 * c] = hh[0]; hi[2 * c + 1] = hh[1]; }
+        if (rad_max) rad_max[c] = rm;
+        if (rad_ip) rad_ip[c] = ri;
+        if (hull_area) hull_area[c] = area;
+        if (hull_start) hull_start[c + 1] = nh;
     }
     return DBAT_HIP_OK;
     API_CATCH

@@ -528,6 +528,103 @@ def ray_angles(s, E=None, device=0):
     return NS(op=op, cam=cam, op_rays=op_rays, cam_rays=cam_rays)
 
 
+def _corner_radius(s, i):
+    """Largest distance of an image corner to the principal point of image i, mm (coverage.m:140-147 as
+    report._coverage restates it)."""
+    px, pp, im = s.IO.sensor.pxSize[:, i], s.IO.val[1:3, i], s.IO.sensor.imSize[:, i]
+    xx, yy = np.array([0.5, im[0] + 0.5]), np.array([0.5, im[1] + 0.5])
+    cu, cv = xx[[0, 0, 1, 1]], yy[[0, 1, 1, 0]]
+    return np.sqrt((cu * px[0] - pp[0]) ** 2 + (-cv * px[1] - pp[1]) ** 2).max()
+
+
+def _hull_area_of(pts):
+    """Vertices (indices into the 2-by-n points, counter-clockwise from the lowest (u, v), strictly extreme) and area
+    of the convex hull of a small point set on the host: the monotone chain and the shoelace sum relative to the
+    minimum, as the device kernel forms them."""
+    n = pts.shape[1]
+    order = sorted(range(n), key=lambda i: (pts[0, i], pts[1, i], i))
+    order = [i for k, i in enumerate(order) if k == 0 or (pts[:, i] != pts[:, order[k - 1]]).any()]
+    if len(order) < 3:
+        return order, 0.0
+
+    def half(seq):
+        h = []
+        for i in seq:
+            while len(h) >= 2:
+                a, b = pts[:, h[-2]], pts[:, h[-1]]
+                if (b[0] - a[0]) * (pts[1, i] - a[1]) - (b[1] - a[1]) * (pts[0, i] - a[0]) <= 0:
+                    h.pop()
+                else:
+                    break
+            h.append(i)
+        return h
+    h = half(order)[:-1] + half(order[::-1])[:-1]
+    if len(h) < 3:
+        return h, 0.0
+    q = pts[:, h] - pts.min(1, keepdims=True)
+    return h, 0.5 * float(np.sum(q[0] * np.roll(q[1], -1) - np.roll(q[0], -1) * q[1]))
+
+
+def network_quality(s, E=None, device=0):
+    """Image coverage and marking-residual statistics of the network in s, from the device (dbat_hip_coverage,
+    dbat_hip_residual_stats) on the handle bundle() left behind -- photogrammetry/coverage.m and the "Point Marking
+    Residuals" block of the result file at any size, without the dense visibility table.  Evaluated at the values in s.
+      coverage   per image: lo, hi (2, nImages), rad_ip, hull (list of IP-column arrays, counter-clockwise, the closing
+                 point not repeated), hull_area [px^2], rad_max [mm], points; with s.IO.sensor.imSize also the
+                 fractions c (convex hull), cr (rectangular), crr (radial) of coverage.m -- NaN for an image without
+                 points, as coverage.m leaves them
+      coverage_union(cams) -> (c, cr, crr, lo, hi, hull_area) for the images cams together (coverage.m, union=true:
+                 image size and principal point of the first one; 0 where none has points), from the per-image
+                 results alone: the hull over the per-image hull vertices
+      residuals  rms, max, max_ip, op_rms, op_rays, cam_rms, cam_points (pixels; NaN for a zero count)"""
+    h = _hip.acquire(s, device)
+    done = False
+    try:
+        cov = h.coverage()
+        st = h.residual_stats(h.serialize())
+        done = True
+    finally:
+        _hip.release(h, keep=done)
+    nc = s.EO.val.shape[1]
+    have_im = hasattr(s.IO.sensor, 'imSize')
+    cam_n = st['cam_n']
+    c = NS(lo=cov['lo'], hi=cov['hi'], rad_ip=cov['rad_ip'], rad_max=cov['rad_max'], hull=cov['hull'],
+           hull_area=cov['hull_area'], points=cam_n)
+    if have_im:
+        tot = np.prod(np.asarray(s.IO.sensor.imSize, float), 0)
+        some = cam_n > 0
+        c.c = np.where(some, cov['hull_area'] / tot, np.nan)
+        with np.errstate(invalid='ignore'):
+            c.cr = np.where(some, np.prod(cov['hi'] - cov['lo'], 0) / tot, np.nan)
+            c.crr = np.where(some, cov['rad_max'] / np.array([_corner_radius(s, i) for i in range(nc)]), np.nan)
+    uv = np.asarray(s.IP.val, float)
+
+    def coverage_union(cams):
+        cams = np.asarray(cams, np.int64).ravel()
+        used = cams[cam_n[cams] > 0]
+        if len(used) == 0:
+            return (0.0, 0.0, 0.0, np.full(2, np.nan), np.full(2, np.nan), 0.0)
+        i = int(cams[0])
+        lo, hi = cov['lo'][:, used].min(1), cov['hi'][:, used].max(1)
+        cols = np.concatenate([cov['hull'][k] for k in used])
+        area = _hull_area_of(uv[:, cols])[1]
+        if not have_im:
+            return (np.nan, np.nan, np.nan, lo, hi, area)
+        # the largest radius about the FIRST image's principal point: a maximum of a convex function over the points
+        # is attained at a vertex of their hull, so the per-image hull vertices suffice
+        px, pp = s.IO.sensor.pxSize[:, i], s.IO.val[1:3, i]
+        rad = np.sqrt((uv[0, cols] * px[0] - pp[0]) ** 2 + (-uv[1, cols] * px[1] - pp[1]) ** 2).max()
+        tot = float(np.prod(s.IO.sensor.imSize[:, i]))
+        return (area / tot, float(np.prod(hi - lo)) / tot, rad / _corner_radius(s, i), lo, hi, area)
+
+    no = int(cam_n.sum())
+    with np.errstate(divide='ignore', invalid='ignore'):
+        res = NS(rms=float(np.sqrt(st['total_ss'] / no)) if no else np.nan, max=st['max_e'], max_ip=st['max_ip'],
+                 op_rms=np.sqrt(st['op_ss'] / st['op_n']), op_rays=st['op_n'],
+                 cam_rms=np.sqrt(st['cam_ss'] / cam_n), cam_points=cam_n)
+    return NS(coverage=c, coverage_union=coverage_union, residuals=res)
+
+
 def _reapply_weights(h, E):
     """A robust bundle's weight factors on an acquired handle (acquire() -> set_values restored the base weights):
     covariance and redundancy then describe the final reweighted system.  Returns E.robust."""

@@ -20,6 +20,10 @@ none -- the report stops after the iteration summary.
 point_angles=(op, op_rays) (optional keyword of both; radians and ray counts as
 dbat_amd.ray_angles returns them): the "Point Angles" block is written from
 them instead of the host loop over the points and the dense visibility table.
+
+quality=q (optional keyword of both; what dbat_amd.network_quality returns): the
+"Photo point coverage", "Point Measurements" and "Point Marking Residuals" blocks
+are written from q; together with point_angles= neither _vis nor _coverage runs.
 """
 from __future__ import annotations
 
@@ -206,7 +210,7 @@ def _angles(s, vis):
     return a
 
 
-def _quality_lines(s, E, COP, vop, point_angles=None):
+def _quality_lines(s, E, COP, vop, point_angles=None, quality=None):
     p, p2, p3, p4, p5, p6 = (_P * k for k in range(1, 7))
     out = [p + 'Quality', p2 + 'Photographs']
     ne = s.EO.val.shape[1]
@@ -222,8 +226,14 @@ def _quality_lines(s, E, COP, vop, point_angles=None):
         out += _pretty(p4, [('Calibration:', 'yes' if est_io[:, i].any() else '<not available>'),
                             ('Number of photos using camera:', '%d' % len(cams))])
         if have_im:
-            c, cr, crr = _coverage(s, cams, False)
-            uc, ucr, ucrr = _coverage(s, cams, True)
+            if quality is None:
+                c, cr, crr = _coverage(s, cams, False)
+                uc, ucr, ucrr = _coverage(s, cams, True)
+            else:
+                # precomputed (dbat_amd.network_quality); an image without points counts as 0, as _coverage has it
+                qc = quality.coverage
+                c, cr, crr = (np.where(qc.points[cams] > 0, v[cams], 0.0) for v in (qc.c, qc.cr, qc.crr))
+                uc, ucr, ucrr = quality.coverage_union(cams)[:3]
             rnd = lambda v: int(np.floor(v * 100 + 0.5))
             fmt = lambda a, u: '%d%%-%d%% (%d%% average, %d%% union)' % (rnd(a.min()), rnd(a.max()), rnd(a.mean()), rnd(u))
             out.append(p4 + 'Photo point coverage:')
@@ -236,8 +246,12 @@ def _quality_lines(s, E, COP, vop, point_angles=None):
     npnt = s.OP.val.shape[1]
     ctrl = np.asarray(getattr(s.prior.OP, 'isCtrl', np.zeros(npnt, bool)), bool)
     chk = np.asarray(getattr(s.prior.OP, 'isCheck', np.zeros(npnt, bool)), bool)
-    vis, ipix = _vis(s)
-    rays = vis.sum(1)
+    # with quality= the ray counts and the residual block come from the device; the dense table is then built only
+    # for the angles (and not at all with point_angles= as well)
+    vis = None
+    if quality is None or point_angles is None:
+        vis, ipix = _vis(s)
+    rays = vis.sum(1) if quality is None else np.asarray(quality.residuals.op_rays).astype(np.int64)
     out.append(p2 + 'Point Measurements')
     out.append(p3 + 'Number of control pts: %d' % ctrl.sum())
     out.append(p3 + 'Number of check pts: %d' % chk.sum())
@@ -267,18 +281,27 @@ def _quality_lines(s, E, COP, vop, point_angles=None):
         out.append(p3 + 'OP ray count: -')
     # ---- Point marking residuals (:630-672, bundle_residuals.m)
     ids = np.asarray(s.OP.id)
-    pt_res = np.sqrt(np.sum(np.asarray(s.post.res.IP, float) ** 2, 0))
-    res = np.zeros(vis.shape)
-    res[s.IP.pt, s.IP.cam] = pt_res
     out.append(p2 + 'Point Marking Residuals')
-    out.append(p3 + 'Overall point RMS: %.3f pixels' % np.sqrt(np.mean(pt_res ** 2)))
-    out.append(p3 + 'Mark point residuals:')
-    k = int(np.argmax(res.flatten('F')))
-    out.append(p4 + 'Maximum: %.3f pixels (OP %d on photo %d)' % (res.flatten('F')[k], ids[k % npnt], k // npnt + 1))
-    with np.errstate(divide='ignore', invalid='ignore'):
-        mean_op = np.sqrt((res ** 2).sum(1) / rays)
-        n_photo = vis.sum(0)
-        mean_photo = np.sqrt((res ** 2).sum(0) / n_photo)
+    if quality is None:
+        pt_res = np.sqrt(np.sum(np.asarray(s.post.res.IP, float) ** 2, 0))
+        res = np.zeros(vis.shape)
+        res[s.IP.pt, s.IP.cam] = pt_res
+        out.append(p3 + 'Overall point RMS: %.3f pixels' % np.sqrt(np.mean(pt_res ** 2)))
+        out.append(p3 + 'Mark point residuals:')
+        k = int(np.argmax(res.flatten('F')))
+        out.append(p4 + 'Maximum: %.3f pixels (OP %d on photo %d)' % (res.flatten('F')[k], ids[k % npnt], k // npnt + 1))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            mean_op = np.sqrt((res ** 2).sum(1) / rays)
+            n_photo = vis.sum(0)
+            mean_photo = np.sqrt((res ** 2).sum(0) / n_photo)
+    else:
+        qr = quality.residuals
+        out.append(p3 + 'Overall point RMS: %.3f pixels' % qr.rms)
+        out.append(p3 + 'Mark point residuals:')
+        k = int(qr.max_ip)
+        out.append(p4 + 'Maximum: %.3f pixels (OP %d on photo %d)' % (qr.max, ids[s.IP.pt[k]], s.IP.cam[k] + 1))
+        mean_op, mean_photo = np.asarray(qr.op_rms, float), np.asarray(qr.cam_rms, float)
+        n_photo = np.asarray(qr.cam_points).astype(np.int64)
     out.append(p3 + 'Object point residuals (RMS over all images of a point):')
     a, b = int(np.nanargmin(mean_op)), int(np.nanargmax(mean_op))
     out.append(p4 + 'Minimum: %.3f pixels (OP %d over %d images)' % (mean_op[a], ids[a], rays[a]))
@@ -416,7 +439,7 @@ def _quality_lines(s, E, COP, vop, point_angles=None):
     return out
 
 
-def bundle_result_lines(s, E, CIO=None, CEO=None, COP=None, point_angles=None):
+def bundle_result_lines(s, E, CIO=None, CEO=None, COP=None, point_angles=None, quality=None):
     p, p2, p3, p4, p5, p6 = (_P * k for k in range(1, 7))
     have_cov = CIO is not None and CEO is not None and COP is not None
     est_io = np.asarray(s.bundle.est.IO, bool)
@@ -583,12 +606,12 @@ def bundle_result_lines(s, E, CIO=None, CEO=None, COP=None, point_angles=None):
                 vals.append((corr_str, ','.join(' %s:%.1f%%' % (enames[pos_of[b]], v * 100) for b, v in hits) + '.'))
             out.append(p5 + nme + ':')
             out += _pretty(p6, vals, pad, pad)
-    return out + _quality_lines(s, E, COP, vop, point_angles)
+    return out + _quality_lines(s, E, COP, vop, point_angles, quality)
 
 
-def bundle_result_file(s, E, CIO=None, CEO=None, COP=None, path='report.txt', point_angles=None):
+def bundle_result_file(s, E, CIO=None, CEO=None, COP=None, path='report.txt', point_angles=None, quality=None):
     lines = ['Damped Bundle Adjustment Toolbox result file']
-    lines += bundle_result_lines(s, E, CIO, CEO, COP, point_angles=point_angles)
+    lines += bundle_result_lines(s, E, CIO, CEO, COP, point_angles=point_angles, quality=quality)
     with open(path, 'w') as fh:
         fh.write('\n'.join(lines) + '\n')
     return lines

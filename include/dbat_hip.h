@@ -500,6 +500,43 @@ int  dbat_hip_ray_angles(dbat_hip_handle *h, const double *x, double *op_angle, 
  * ip_pt), for tests of the definition; never on the product path.  Either output may be NULL. */
 int  dbat_hip_debug_ray_angles_host(const dbat_hip_problem *prob, double *op_angle, double *cam_angle);
 
+/* Image coverage by the measured points (photogrammetry/coverage.m:113-185), per image, from the pixel coordinates
+ * alone (no x).  Image c owns the IP columns of its points (IP is image-major); every index below is an IP column.
+ *   lo, hi      [2*n_images] exact min and max of u and v; NaN for an image without points
+ *   rad_max     [n_images] largest distance to the principal point, mm: sqrt((u px_u - pp_x)^2 + (-v px_v - pp_y)^2),
+ *               pp = IO_val rows 1, 2 of the image's column (the values of the last dbat_hip_set_values); NaN for none
+ *   rad_ip      [n_images] the column that attains it (ties: the lowest), -1 for none
+ *   hull_area   [n_images] area of the convex hull, px^2: the shoelace sum over its vertices relative to lo; 0 for
+ *               fewer than three points or collinear points
+ *   hull_start  [n_images+1], hull_ip [n_obs capacity]: the hull of image c is hull_ip[hull_start[c] ..
+ *               hull_start[c+1]), counter-clockwise (u to the right, v up) from the lowest (u, v) in lexicographic
+ *               order, strictly extreme points only (no collinear boundary points; of equal points the lowest
+ *               column); fewer than three distinct points: those points
+ * Any output may be NULL.  One workgroup per image (csrc/quality.hpp): the points outside the octagon of the eight
+ * extreme points are sorted and scanned (monotone chain), at most dbat_hip_quality_hull_cap() of them in LDS, more in
+ * global memory.  The scan ends after a number of steps bounded by the point count for every input.  Two calls give
+ * the same bits.  What the call needs beyond the plan's uploads is built by the first call and kept on the handle.
+ * A handle that is one shard of several (shard_count > 1) returns DBAT_HIP_EINVAL. */
+int  dbat_hip_coverage(dbat_hip_handle *h, double *lo, double *hi, double *rad_max, int64_t *rad_ip, double *hull_area,
+                       int64_t *hull_start, int64_t *hull_ip);
+/* Marking-residual statistics at x (file/bundle_result_file.m:630-672): with e_i the 2-norm of image point i's
+ * residual in pixels (the residual pass's mm rows divided by the image's px_size),
+ *   cam_n, cam_ss  [n_images] points of every image and the sum of e^2 over them (IP order)
+ *   op_n, op_ss    [n_points] rays of every object point and the sum of e^2 over them (the plan's point-major order)
+ *   total_ss       the sum of e^2 over all image points      max_e, max_ip  the largest e and its IP column (ties: the
+ *                  lowest column, the order of the reference's res(:)); NaN and -1 without image points
+ * Any output may be NULL.  Every sum is a reduction in a fixed order, no floating-point atomics: two calls give the
+ * same bits.  RMS values (and the NaN of a zero count) are the caller's.  A handle that is one shard of several
+ * returns DBAT_HIP_EINVAL. */
+int  dbat_hip_residual_stats(dbat_hip_handle *h, const double *x, int64_t *cam_n, double *cam_ss, int64_t *op_n,
+                             double *op_ss, double *total_ss, double *max_e, int64_t *max_ip);
+/* Candidates of one image that dbat_hip_coverage sorts in LDS (QUAL_HULL_CAP). */
+int32_t dbat_hip_quality_hull_cap(void);
+/* Host only, one thread, no GPU: dbat_hip_coverage over the problem's own arrays (ip_cam, ip_val, px_size, IO_val)
+ * with the kernel's own filter, order, chain scan and shoelace sum; for tests, never on the product path. */
+int  dbat_hip_debug_coverage_host(const dbat_hip_problem *prob, double *lo, double *hi, double *rad_max, int64_t *rad_ip,
+                                  double *hull_area, int64_t *hull_start, int64_t *hull_ip);
+
 /* ---- robust estimation: iteratively reweighted least squares over the image points -------------------------------
  * For image point i (one IP column, two rows) at parameters x:
  *   s_i   = ||(w_u v_u, w_v v_v)||_2, w = 1 / (IP.std * pxSize) the BASE weights, v the unweighted residual
