@@ -441,6 +441,37 @@ def relerr(a, b):
     return np.linalg.norm((a - b).ravel()) / (d if d > 0 else 1.0)
 
 
+TOL_LIN = 1e-10         # column norms, trace(J'J), ||J v||^2 and J v: the bars of test_hip_parity.py::test_step_parity
+
+
+def linearisation_figures(h, J, trace_h):
+    """The quantities of handle h's last linearisation that no step shows, against the oracle's weighted sparse J at
+    the same point: relative errors of the column norms (sqrt(sum J o J, axis 0)), of trace_h (st['trace'] of that
+    linearisation) against (J'J).diagonal().sum(), and with v = default_rng(2).standard_normal(n) of ||J v||^2 and
+    of J v (image rows in the reference's row order).  Column norms squared, trace and ||J v||^2 are sums of
+    non-negative f64 terms, at most about 1e4 per column: n 2^-53 is about 1e-12, two orders below TOL_LIN.  That
+    holds column by column, and the vector's relerr is blind to the point columns beside a distortion column of 1e10
+    (a quarter too much on every heavy point's norm is 9e-10 of giant-mfma's vector): 'worst_column' is the largest
+    relative error of one column norm."""
+    J = J.tocsc()
+    Jn = np.sqrt(np.asarray(J.multiply(J).sum(0)).ravel())
+    tr = float((J.T @ J).diagonal().sum())
+    v = np.random.default_rng(2).standard_normal(J.shape[1])
+    Jv = J @ v
+    Jn_h = h.colnorms()
+    assert Jn.min() > 0
+    return dict(colnorms=relerr(Jn_h, Jn), worst_column=float(np.abs(Jn_h / Jn - 1).max()), trace=abs(trace_h - tr) / tr,
+                JvJv=abs(h.jtimes_sqnorm(v) - Jv @ Jv) / (Jv @ Jv), Jv=relerr(h.jtimes(v), Jv))
+
+
+def check_linearisation_figures(fig, label):
+    """Prints the figures of linearisation_figures, then holds each to TOL_LIN."""
+    print('linearisation %-44s colnorms %.2e  trace %.2e  JvJv %.2e  Jv %.2e  worst column %.2e'
+          % (label, fig['colnorms'], fig['trace'], fig['JvJv'], fig['Jv'], fig['worst_column']))
+    for k in ('colnorms', 'worst_column', 'trace', 'JvJv', 'Jv'):
+        assert fig[k] < TOL_LIN, '%s: %s of the linearisation off by %.2e' % (label, k, fig[k])
+
+
 def script_forwintersect(s):
     """The script operation forward_intersection: on the device where there is one (the product path,
     dbat_amd.loadtables.forwintersect -> dbat_hip_forwintersect), by the oracle's restatement on the CPU box."""

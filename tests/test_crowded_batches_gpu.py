@@ -11,7 +11,7 @@ import pytest
 import scipy.sparse as sp
 
 import dbat_oracle as o
-from helpers import crowded_struct, relerr
+from helpers import check_linearisation_figures, crowded_struct, linearisation_figures, relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -93,7 +93,8 @@ def oracle_setup(s):
 @pytest.mark.parametrize('route,kind', STEP_CASES, ids=['%s-%s' % c for c in STEP_CASES])
 def test_step_parity_crowded_batches(hip, route, kind, monkeypatch):
     """One linearisation + solve, scaled Gauss-Newton and damped, against the oracle's full sparse normal equations;
-    the gradient and the step's scalars as in test_hip_parity.py::test_step_parity."""
+    the gradient and the step's scalars as in test_hip_parity.py::test_step_parity, and its column norms, trace(J'J),
+    ||J v||^2 and J v (bar 1e-10; largest on the MI355X over the 22 cases: 5.6e-16, 5.9e-16, 5.8e-16, 1.0e-15)."""
     s = scene(route, kind, monkeypatch)
     so, x0, w = oracle_setup(s)
     R = np.sqrt(w)
@@ -115,8 +116,10 @@ def test_step_parity_crowded_batches(hip, route, kind, monkeypatch):
         assert abs(st['rJp'] - r @ Jp) <= 1e-7 * abs(r @ Jp)
         assert abs(st['pp'] - p_o @ p_o) <= 1e-7 * (p_o @ p_o)
         assert relerr(h.gradient(), J.T @ r) < 1e-10
-        q_h, _ = h.linearize_solve(x0, lam, False)
+        q_h, st2 = h.linearize_solve(x0, lam, False)
         assert relerr(q_h, q_o) < TOL_STEP
+        # what no step shows (the scaled step is invariant under any column scaling): column norms, trace(J'J), J v
+        check_linearisation_figures(linearisation_figures(h, J, st2['trace']), '%s-%s' % (route, kind))
     finally:
         h.close()
 

@@ -36,6 +36,38 @@ Largest relerr of the scaled Gauss-Newton step against the oracle, per route and
   all-see-all                  1.8e-12   1.3e-12           1.7e-12              6.4e-13
 Bundle with omega set against the oracle's (relerr of x): tile2 6.8e-17, heavy-selfcal 1.3e-16, giant-selfcal 4.3e-16;
 covariance blocks, of the largest entry: 1.7e-12, 1.0e-12, 6.9e-11.
+
+What no step shows -- the scaled step is invariant under any diagonal column scaling, and a wrong trace only sends
+Levenberg-Marquardt down another path: per route and way the relative errors of the column norms, of trace(J'J)
+(st['trace'] of the damped build), of ||J v||^2 and of J v against the oracle's weighted sparse J
+(helpers.linearisation_figures; MI355X; the bar is 1e-10, 'plan' the larger of the two bases).  None is above 1e-11;
+the largest, the trace of the self-calibrating giant and mixed scenes, are sums over camera columns of 1e20 and more.
+The largest relative error of a single column norm (same bar; the vector's relerr is blind to the point columns
+beside such a camera column) over all routes and ways, weighted and on the crowded routes: 1.3e-15 (giant-mfma).
+  route                      plan                              promoted-uniform                  promoted-nonuniform
+                             colnorms trace  JvJv    Jv        colnorms trace  JvJv    Jv        colnorms trace  JvJv    Jv
+  sig                        1.1e-16 0       3.6e-16 2.2e-16   1.1e-16 0       2.0e-16 2.2e-16   1.1e-16 2.1e-16 1.8e-16 2.3e-16
+  tile3                      9.9e-17 0       3.7e-16 2.1e-16   1.0e-16 0       1.9e-16 2.3e-16   1.1e-16 0       1.8e-16 2.2e-16
+  tile2                      1.2e-16 2.6e-15 5.3e-16 6.1e-16   1.6e-18 2.1e-15 5.3e-16 6.5e-16   2.3e-16 2.7e-15 3.6e-16 4.7e-16
+  heavy                      1.3e-16 1.4e-16 3.6e-16 2.1e-16   9.4e-17 0       0       2.3e-16   1.2e-16 0       4.8e-16 2.1e-16
+  heavy-selfcal              1.2e-16 9.9e-16 6.1e-16 5.4e-16   1.2e-16 2.7e-16 8.1e-16 3.5e-16   1.1e-18 9.9e-16 4.9e-16 5.4e-16
+  columns                    1.2e-16 2.4e-16 5.4e-16 2.2e-16   1.1e-16 1.2e-16 0       2.2e-16   1.1e-16 2.2e-16 5.4e-16 2.3e-16
+  columns-selfcal            4.0e-16 2.9e-15 1.2e-15 7.9e-16   4.0e-16 2.9e-15 1.2e-15 6.4e-16   1.1e-20 5.7e-16 4.3e-16 8.0e-16
+  bt128                      1.6e-16 2.1e-16 1.8e-16 2.2e-16   1.6e-16 1.2e-16 0       2.3e-16   1.4e-16 2.1e-16 1.8e-16 2.2e-16
+  giant                      1.6e-16 0       1.4e-16 2.2e-16   1.5e-16 0       0       2.3e-16   1.6e-16 0       1.2e-16 2.3e-16
+  giant-selfcal              4.3e-16 2.1e-14 5.0e-16 2.1e-16   2.1e-16 2.1e-14 1.2e-16 1.9e-16   4.3e-16 1.5e-14 2.5e-16 2.7e-16
+  giant-mfma                 3.6e-16 3.7e-16 4.4e-16 4.7e-16   3.1e-16 3.7e-16 2.5e-16 3.4e-16   3.8e-16 2.0e-16 4.4e-16 4.6e-16
+  giant-mfma-selfcal-groups3 4.2e-16 3.5e-15 2.3e-16 1.3e-16   2.1e-16 2.8e-15 2.3e-16 6.3e-17   2.1e-16 2.9e-15 2.3e-16 1.2e-16
+  mixed-heavy                1.8e-16 9.6e-15 0       6.4e-16   7.0e-19 9.3e-15 0       6.6e-16   1.1e-16 7.3e-15 0       6.3e-16
+  mixed-columns              3.5e-16 1.7e-14 0       6.6e-16   7.2e-16 7.4e-15 2.2e-16 6.5e-16   3.5e-16 1.7e-14 1.9e-16 6.8e-16
+  all-see-all                1.4e-16 2.0e-15 1.5e-16 4.9e-16   1.4e-16 2.0e-15 1.5e-16 4.9e-16   1.6e-16 2.1e-15 1.3e-16 3.5e-16
+The trace-only pass (lambda0 of one LM iteration against the oracle's trace; the bar is 1e-11): at most 1.1e-15 on the
+eight routes and three ways, 1.7e-16 from the signature kernel's pass 1 on two ranks.
+The damping loops with omega set, both ways (relerr of x against the oracle's loop): 'lm' and 'lmp' at most 5.4e-16
+with the oracle's 5 and 3 iterations; 'gm' 1.1e-16 where it runs (tile3, heavy) and the oracle's code -2 at
+iteration 0 on the self-calibrating scenes.  LM at convTol = 1e-3 (its margins: the table above
+test_lm_iteration_count_with_weights): the oracle's count, objective values to 5.7e-16 of the largest (giant-selfcal
+4.2e-12).
 """
 import copy
 from types import SimpleNamespace as NS
@@ -45,7 +77,8 @@ import pytest
 import scipy.sparse as sp
 
 import dbat_oracle as o
-from helpers import (all_see_all_scene, base_image_weights, camcal_struct, giant_points_struct, mixed_heavy_struct,
+from helpers import (TOL_LIN, all_see_all_scene, base_image_weights, camcal_struct, check_linearisation_figures,
+                     crowded_struct, giant_points_struct, linearisation_figures, lm_decision_margins, mixed_heavy_struct,
                      obs_weight_factors, relerr, reweighted_struct, std_pattern, sxb_prior_eo_struct, synth_struct)
 from test_crowded_batches_gpu import ROUTES, check_route, oracle_setup
 from test_crowded_batches_gpu import scene as crowded_scene
@@ -130,15 +163,18 @@ def oracle_system(s_eff):
     JTJ = (J.T @ J).tocsc()
     lam = 1e-4 * JTJ.diagonal().sum() / J.shape[1]
     q, _ = o.normal_solve((JTJ + lam * sp.identity(J.shape[1])).tocsc(), -(J.T @ r))
-    return NS(x0=x0, r=r, J=J, p=p, lam=lam, q=q, g=J.T @ r)
+    return NS(x0=x0, r=r, J=J, p=p, lam=lam, q=q, g=J.T @ r, Jn=np.sqrt(np.asarray(J.multiply(J).sum(0)).ravel()),
+              trace=float(JTJ.diagonal().sum()))
 
 
 FIGURES = {}
+LIN_FIGURES = {}
 
 
 def check_against_oracle(h, O, w_rows, label):
     """Step, scalars, gradient, damped step, cost and the weighted residual rows of handle h against the oracle's
-    system O; w_rows (nObs, 2): the weights base * sqrt(omega) the image rows must carry.  Returns the step."""
+    system O, and the column norms, trace(J'J), ||J v||^2 and J v of its linearisation (helpers.linearisation_figures);
+    w_rows (nObs, 2): the weights base * sqrt(omega) the image rows must carry.  Returns the step."""
     x0 = O.x0
     p_h, st = h.linearize_solve(x0, 0.0, True)
     FIGURES[label] = relerr(p_h, O.p)
@@ -153,9 +189,14 @@ def check_against_oracle(h, O, w_rows, label):
     ru, rw = h.final_residuals()                        # rows of the linearisation at x0
     n2 = 2 * w_rows.shape[0]
     assert np.allclose(rw[:n2].reshape(-1, 2), ru[:n2].reshape(-1, 2) * w_rows, rtol=1e-12, atol=1e-300)
-    q_h, _ = h.linearize_solve(x0, O.lam, False)
+    # what no step shows (the scaled step is invariant under any diagonal column scaling): the column norms the build
+    # kernels write beside it, below those of the damped build with trace(J'J) and J v
+    assert relerr(h.colnorms(), O.Jn) < TOL_LIN
+    q_h, st2 = h.linearize_solve(x0, O.lam, False)
     print('relerr damped step %-41s %.2e' % (label, relerr(q_h, O.q)))
     assert relerr(q_h, O.q) < TOL_STEP
+    LIN_FIGURES[label] = linearisation_figures(h, O.J, st2['trace'])
+    check_linearisation_figures(LIN_FIGURES[label], label)
     _, f = h.residual(x0)
     assert abs(f - 0.5 * (O.r @ O.r)) <= 1e-12 * 0.5 * (O.r @ O.r)
     return p_h
@@ -189,6 +230,97 @@ def test_weighted_step_three_ways(hip, name, base, monkeypatch):
         h.close()
     print('relerr promoted against plan %-31s %.2e' % ('%s %s' % (name, base), relerr(p_prom, p_plan)))
     assert relerr(p_prom, p_plan) <= 1e-9
+
+
+# ---------------------------------------------------------------- the trace-only pass
+TRACE_SCENES = ['sig', 'tile3', 'tile2', 'heavy-selfcal', 'columns', 'bt128', 'giant-selfcal', 'all-see-all']
+WAYS = ('plan', 'promoted-uniform', 'promoted-nonuniform')
+
+
+def weighted_handle(hip, s, om, way):
+    """A handle that carries omega by `way` ('plan': built on the reweighted struct; else set_obs_weights on the
+    struct's own handle), and the struct it was built on."""
+    if way == 'plan':
+        t = reweighted_struct(s, om)
+        return hip.Handle(t), t
+    h = hip.Handle(s)
+    try:
+        h.set_obs_weights(om)
+    except BaseException:
+        h.close()
+        raise
+    return h, s
+
+
+def lm_first_lambda(hip, h, x0):
+    """damp[0] of one Levenberg-Marquardt iteration from x0, which must have come from the trace-only pass."""
+    opt = hip.default_options('lm')
+    opt.store_trace, opt.max_iter = 0, 1
+    x, r, rr, damp, aux, T = h.solve(x0, opt)
+    assert r.n_trace_only == 1
+    return damp[0], abs(opt.lambda0)
+
+
+@pytest.mark.parametrize('name', TRACE_SCENES)
+def test_trace_only_pass_with_weights(hip, name, monkeypatch):
+    """Levenberg-Marquardt's lambda0 = c trace(J'J) / n from the streaming pass that forms no normal equations
+    (k_trace_cm reading cm_w), with weights set in each of the three ways: the oracle's trace of the weighted J, and
+    the trace a full linearisation on the same handle reports.  A wrong lambda0 leaves LM converging by another
+    path, so no bundle test sees it."""
+    s0 = make_scene(name, monkeypatch)
+    for k, way in enumerate(WAYS):
+        s = std_pattern(s0) if way == 'promoted-nonuniform' else s0
+        om = scene_omega(name, s, 10 + k)
+        so, x0o, w = oracle_setup(reweighted_struct(s, om))
+        _, K = o.brown_euler_cam4(x0o, so, jac=True)
+        tr = float((sp.diags(w) @ K.multiply(K)).sum())
+        h, t = weighted_handle(hip, s, om, way)
+        try:
+            check_ran(hip, h, t, name)
+            x0 = h.serialize()
+            assert np.array_equal(x0, x0o)
+            lam0, c = lm_first_lambda(hip, h, x0)
+            print('trace-only pass %-15s %-20s lambda0 off the oracle\'s by %.2e' % (name, way, abs(lam0 - c * tr / h.n) / lam0))
+            assert abs(lam0 - c * tr / h.n) <= 1e-11 * lam0, way
+            _, st = h.linearize_solve(x0, 0.0, False)
+            assert abs(lam0 - c * st['trace'] / h.n) <= 1e-12 * lam0, way
+        finally:
+            h.close()
+
+
+@pytest.mark.parametrize('way', WAYS[:2])
+def test_trace_only_build_with_weights_two_ranks(hip, way, monkeypatch):
+    """With several ranks the trace comes from a build instead of k_trace_cm: on the signature route from
+    build_sig_tile's pass 1 (reading sg_w), which leaves before the Schur complement under d.trace_only.  Two ranks
+    of one GPU on the 'sig' scene, the same two assertions on every rank."""
+    from test_multishard_gpu import _run_ranks
+    name = 'sig'
+    s = make_scene(name, monkeypatch)
+    om = scene_omega(name, s, 13)
+    so, x0o, w = oracle_setup(reweighted_struct(s, om))
+    _, K = o.brown_euler_cam4(x0o, so, jac=True)
+    tr = float((sp.diags(w) @ K.multiply(K)).sum())
+    t = reweighted_struct(s, om) if way == 'plan' else s
+    assert hip.plan_layout_stats(t, 0, 2)['build_sig'] and hip.plan_layout_stats(t, 1, 2)['build_sig']
+
+    def work(comm):
+        hh = hip.Handle(t, shard_rank=comm.rank, shard_count=comm.world_size)
+        try:
+            hh.set_allreduce(comm.allreduce_ptr)
+            if way != 'plan':
+                hh.set_obs_weights(om)
+            assert hh.build_kernel_name() == 'k_build_sig'
+            lam0, c = lm_first_lambda(hip, hh, x0o)
+            _, st = hh.linearize_solve(x0o, 0.0, False)
+            return lam0, c, st['trace'], hh.n
+        finally:
+            hh.close()
+
+    out, _ = _run_ranks(s, 2, work)
+    for lam0, c, tr_h, n in out:
+        print('trace-only build, two ranks, %-17s lambda0 off the oracle\'s by %.2e' % (way, abs(lam0 - c * tr / n) / lam0))
+        assert abs(lam0 - c * tr / n) <= 1e-11 * lam0
+        assert abs(lam0 - c * tr_h / n) <= 1e-12 * lam0
 
 
 # ---------------------------------------------------------------- covariance
@@ -231,6 +363,114 @@ def test_bundle_and_covariance_promoted(hip, name, monkeypatch):
         assert A.shape == B.shape and abs(B).max() > 0
         print('covariance %-20s %.2e of the largest entry' % (name, abs(A - B).max() / abs(B).max()))
         assert abs(A - B).max() <= 1e-6 * abs(B).max()
+
+
+# ---------------------------------------------------------------- the damping loops with weights set
+LOOP_SCENES = ['tile2', 'heavy-selfcal', 'giant-selfcal']
+# 'gm' on the three self-calibrating scenes ends in the oracle with code -2 at iteration 0: the UNSCALED normal matrix
+# has diagonal entries from 6 to 2e20 (K3 beside an object point), the estimate (min / max diag L)^2 is 5e-18 / 1e-17 /
+# 4e-22 against eps = 2.2e-16.  There the case pins the code, the first weighted objective and x = x0; the loop itself
+# runs with weights on the two fixed-IO scenes beside them (estimate 8e-8 / 1e-7; 3 and 4 iterations).
+# 'tile2' is built smaller for 'gm' (30 cameras, 1500 points through the same builder; check_ran holds it to the route):
+# the oracle's analysis of the singular 9361-column matrix takes 30 s of CPU, that of the smaller one 4 s.
+GM_SCENES = LOOP_SCENES + ['tile3', 'heavy']
+LOOP_CASES = [(n, d) for d in ('lm', 'lmp') for n in LOOP_SCENES] + [(n, 'gm') for n in GM_SCENES]
+
+
+def loop_scene(name, damping, monkeypatch):
+    if (name, damping) == ('tile2', 'gm'):
+        for k, v in ROUTES[name][0].items():
+            monkeypatch.setenv(k, v)
+        return crowded_struct('prior3', selfcal=True, cams=30, points=1500)[0]
+    return make_scene(name, monkeypatch)
+
+
+def solve_promoted(hip, s, om, damping, name, conv_tol=1e-6):
+    """Handle.solve with omega set on the handle of s: what bundle() returns as E, as far as the checks read it."""
+    h = hip.Handle(s)
+    try:
+        h.set_obs_weights(om)
+        check_ran(hip, h, s, name)
+        opt = hip.default_options(damping)
+        opt.max_iter, opt.conv_tol, opt.store_trace = 20, conv_tol, 0
+        x, res, rr, damp, aux, T = h.solve(h.serialize(), opt)
+        ru, rw = h.final_residuals()
+        dof = h.m - h.n
+    finally:
+        h.close()
+    E = NS(x=x, code=int(res.code), iters=int(res.iters), res=rr, s0=float(np.sqrt(rw @ rw / dof)))
+    if damping == 'lm':
+        E.damping = NS(**{'lambda': damp})
+    elif damping == 'lmp':
+        rho, step = aux[:opt.max_iter + 2], aux[opt.max_iter + 2:]
+        E.damping = NS(delta=damp, rho=rho[~np.isnan(rho)], step=step[~np.isnan(step)].astype(int))
+    return E
+
+
+@pytest.mark.parametrize('name,damping', LOOP_CASES, ids=['%s-%s' % c for c in LOOP_CASES])
+def test_damping_loops_with_weights(hip, name, damping, monkeypatch):
+    """Levenberg-Marquardt, Powell's dog-leg and Gauss-Markov with omega set, both ways, against the oracle's loop of
+    that name on the reweighted struct: the trial-point objective, the gain ratio and the trust-region history all
+    go through weight-reading kernels.  The plan way is bundle() on the reweighted struct, the promoted way
+    Handle.solve after set_obs_weights, as in test_bundle_and_covariance_promoted."""
+    from dbat_amd import bundle
+    from test_hip_parity import check_history
+    s = loop_scene(name, damping, monkeypatch)
+    om = scene_omega(name, s)
+    s_eff = reweighted_struct(s, om)
+    ro, oko, ito, s0o, Eo = o.bundle(s_eff, damping)
+    _, ok, iters, s0, E = bundle(s_eff, damping, reuse_handle=False)
+    Ep = solve_promoted(hip, s, om, damping, name)
+    for way, e, it, sig0 in (('plan', E, iters, s0), ('promoted', Ep, Ep.iters, Ep.s0)):
+        print('relerr %s x %-16s %-9s %.2e (code %d, %d iterations; oracle %d, %d)'
+              % (damping, name, way, relerr(e.x, Eo.x), e.code, it, Eo.code, ito))
+        assert e.code == Eo.code, way
+        assert relerr(e.x, Eo.x) < TOL_X, way
+        assert abs(sig0 - s0o) <= 1e-8 * s0o, way
+        check_history(e, Eo, it, ito, damping)
+        if damping == 'lmp':
+            assert np.array_equal(e.damping.step, Eo.damping.step), way
+            assert relerr(e.damping.delta, Eo.damping.delta) < 1e-9, way
+            assert np.abs(e.damping.rho - Eo.damping.rho).max() < 1e-3, way
+    assert ok == oko
+    assert relerr(Ep.x, E.x) <= 1e-9
+    if damping == 'lmp':
+        assert Ep.iters == iters
+    if damping == 'gm':
+        assert (Eo.code, ito) == (-2, 0) if name in LOOP_SCENES else Eo.code == 0 and ito >= 3      # (the comment above GM_SCENES)
+
+
+# The oracle's LM run at convTol = 1e-3 on the reweighted struct of scene_omega(name, s) (seed 0), helpers.lm_decision_margins:
+#   scene           iterations   smallest margin |fNew - f| / f   termination ratio's factor from 1
+#   tile2           4            5.0e-9                           14.1
+#   heavy-selfcal   4            3.4e-9                           17.2
+#   giant-selfcal   4            3.0e-9                           18.1
+@pytest.mark.parametrize('name', LOOP_SCENES)
+def test_lm_iteration_count_with_weights(hip, name, monkeypatch):
+    """test_hip_parity.py::test_lm_iteration_count_where_it_is_a_property_of_the_problem with omega set, both ways: at
+    convTol = 1e-3 every accept / reject decision of the oracle has a margin three orders above the 1e-12 by which
+    the device's objective values differ from its own (the table above), so the count, the residual history and
+    every lambda must be the oracle's."""
+    from dbat_amd import bundle
+    s = make_scene(name, monkeypatch)
+    om = scene_omega(name, s)
+    s_eff = reweighted_struct(s, om)
+    n_o, margin, term = lm_decision_margins(s_eff, conv_tol=1e-3)
+    assert margin > 1e-10 and term > 1.5, 'not a case for this test any more: margin %.1e, termination factor %.2f' % (margin, term)
+    ro, oko, ito, s0o, Eo = o.bundle(s_eff, 'lm', 1e-3)
+    assert ito == n_o and oko and Eo.code == 0
+    _, ok, iters, s0, E = bundle(s_eff, 'lm', 1e-3, reuse_handle=False)
+    Ep = solve_promoted(hip, s, om, 'lm', name, conv_tol=1e-3)
+    lamo, reso = Eo.damping.__dict__['lambda'], np.asarray(Eo.res)
+    for way, e, it in (('plan', E, iters), ('promoted', Ep, Ep.iters)):
+        assert e.code == 0, way
+        assert it == ito, 'LM iterations (%s): device %d, oracle %d' % (way, it, ito)
+        assert len(e.res) == len(reso) and relerr(e.res, reso) < 1e-8, way
+        lam = e.damping.__dict__['lambda']
+        assert len(lam) == len(lamo) and relerr(lam, lamo) < 1e-8, way
+        print('lm at 1e-3 %-16s %-9s objective values off by %.2e of the largest' % (name, way, np.abs(np.asarray(e.res) - reso).max() / reso.max()))
+        assert np.abs(np.asarray(e.res) - reso).max() <= 1e-11 * reso.max(), way
+        assert relerr(e.x, Eo.x) < TOL_X, way
 
 
 # ---------------------------------------------------------------- redundancy, weighted Jacobian

@@ -43,15 +43,33 @@ def oracle_scale(sn, scale_mode):
     return 1.0 if sc == 0 else sc
 
 
-def oracle_irls(s, loss, k, scale_mode, max_outer=10, tol=1e-3, max_iter=20, conv_tol=1e-6):
-    """The outer loop of dbat_hip_solve_robust on the oracle's Gauss-Newton-Armijo: omega = 1, solve; then evaluate
-    omega' at x, stop if max |omega' - omega| <= tol, else solve again from x with the image rows' weights scaled by
-    omega'.  Returns x, omega, outer (solves), converged, scales, last max change, last code."""
+def oracle_inner_solve(damping):
+    """solve(res, x, w, max_iter, term) -> (x, code, ...): the oracle's damping loop of that name with the arguments
+    its bundle() passes (lambda0 = lambdaMin = -1e-10; delta0 = ||x||, mu = 0.25, eta = 0.75)."""
+    if damping == 'gna':
+        return o.gauss_newton_armijo
+    if damping == 'lm':
+        return lambda res, x, w, mi, term: o.levenberg_marquardt(res, x, w, mi, term, -1e-10, -1e-10)
+    if damping == 'lmp':
+        return lambda res, x, w, mi, term: o.levenberg_marquardt_powell(res, x, w, mi, term, np.linalg.norm(x), 0.25, 0.75)
+    raise ValueError(damping)
+
+
+def oracle_irls(s, loss, k, scale_mode, max_outer=10, tol=1e-3, max_iter=20, conv_tol=1e-6, damping='gna', history=None):
+    """The outer loop of dbat_hip_solve_robust on the oracle's Gauss-Newton-Armijo (or, with `damping`, on its loop of
+    that name): omega = 1, solve; then evaluate omega' at x, stop if max |omega' - omega| <= tol, else solve again
+    from x with the image rows' weights scaled by omega'.  Returns x, omega, outer (solves), converged, scales, last
+    max change, last code.  `history`: a dict that receives 'changes' (every max change) and 'inner_iters' (the
+    iterations of every solve)."""
     so, x, w = _oracle_setup(s)
     no = s.IP.val.shape[1]
     res = lambda t, jac: o.brown_euler_cam4(t, so, jac)
     term = o.term_relative(conv_tol)
-    x, code, *_ = o.gauss_newton_armijo(res, x, w, max_iter, term)
+    solve = oracle_inner_solve(damping)
+    x, code, n, *_ = solve(res, x, w, max_iter, term)
+    hist = dict(changes=[], inner_iters=[n])
+    if history is not None:
+        history.update(hist)
     om = np.ones(no)
     outer, conv, scales, chg = 1, False, [], np.nan
     for _ in range(max_outer):
@@ -62,13 +80,15 @@ def oracle_irls(s, loss, k, scale_mode, max_outer=10, tol=1e-3, max_iter=20, con
         scales.append(sc)
         omn = robust_weight_fn(sn / sc, loss, k)
         chg = float(np.abs(omn - om).max())
+        hist['changes'].append(chg)
         if chg <= tol:
             conv = True
             break
         om = omn
         ww = w.copy()
         ww[:2 * no] = w[:2 * no] * np.repeat(om, 2)
-        x, code, *_ = o.gauss_newton_armijo(res, x, ww, max_iter, term)
+        x, code, n, *_ = solve(res, x, ww, max_iter, term)
+        hist['inner_iters'].append(n)
         outer += 1
     return x, om, outer, conv, scales, chg, code
 
@@ -155,6 +175,22 @@ def test_struct_layout_matches_c(tmp_path):
 def C_sizeof(t):
     import ctypes
     return ctypes.sizeof(t)
+
+
+def test_host_irls_inner_loops():
+    """oracle_irls(damping=...): 'gna' named is the default bit for bit; around Powell's dog-leg the loop recovers the
+    blunders as test_host_irls_recovers_blunders asks of it; an unknown name is refused."""
+    s = blundered('tiny')
+    a = oracle_irls(s, 'huber', 1.5, 'apriori', max_outer=3)
+    b = oracle_irls(s, 'huber', 1.5, 'apriori', max_outer=3, damping='gna')
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2:] == b[2:]
+    hist = {}
+    x, om, outer, conv, scales, chg, code = oracle_irls(s, 'huber', 1.5, 'apriori', max_outer=20, damping='lmp', history=hist)
+    assert code == 0 and conv and outer >= 2 and len(hist['changes']) == len(hist['inner_iters']) == outer and hist['changes'][-1] == chg
+    bad = np.array([5, 40, 77])
+    assert np.all(om[bad] < 0.2) and np.median(om[np.setdiff1d(np.arange(om.size), bad)]) > 0.9
+    with pytest.raises(ValueError):
+        oracle_irls(s, 'huber', 1.5, 'apriori', damping='newton')
 
 
 def test_host_irls_recovers_blunders():
