@@ -5,6 +5,7 @@ Host-side mirror of the reference's interface for the bundle hot path:
     driver       bundle(s, ...) -> (s, ok, iters, sigma0, E); bundle_cov(s, E, 'CIO','CEO','COP');
                  bundle_reliability(s, E): redundancy numbers, standardized residuals, blunder suspects
                  ray_angles(s, E): intersection angles of every object point and every image, ray counts
+                 point_depths(s, E): depth of every object point in every camera that sees it (the chirality veto's test)
                  network_quality(s, E): image coverage and marking-residual statistics, on the device
     loadpm       PhotoModeler export loader (known-answer fixtures)
     initial      resect / forwintersect: initial EO and OP (photogrammetry/resect.m, forwintersect.m)
@@ -14,4 +15,4 @@ Host-side mirror of the reference's interface for the bundle hot path:
     _hip         ctypes binding of include/dbat_hip.h (libdbat_hip.so)
 """
 from .dbatstruct import make_struct, seteoest_depend, validate  # noqa: F401
-from .driver import bundle, bundle_cov, bundle_reliability, ray_angles, network_quality, BadInput  # noqa: F401
+from .driver import bundle, bundle_cov, bundle_reliability, ray_angles, point_depths, network_quality, BadInput  # noqa: F401

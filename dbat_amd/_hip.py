@@ -127,6 +127,14 @@ class RobustResult(C.Structure):
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 
 # every symbol include/dbat_hip.h declares: name -> (restype, argtypes)
+class DepthStats(C.Structure):            # dbat_hip_depth_stats
+    _fields_ = [('n_behind', C.c_int64), ('min_depth', C.c_double), ('argmin_column', C.c_int64)]
+
+
+class VetoStats(C.Structure):             # dbat_hip_veto_stats
+    _fields_ = [('tested', C.c_int64), ('rejected', C.c_int64), ('n_behind', C.c_int64), ('min_depth', C.c_double)]
+
+
 _H = C.c_void_p
 SYMBOLS = {
     'dbat_hip_last_error': (C.c_char_p, []),
@@ -176,6 +184,9 @@ SYMBOLS = {
     'dbat_hip_redundancy': (C.c_int, [_H, _dp, _dp, _dp]),
     'dbat_hip_ray_angles': (C.c_int, [_H, _dp, _dp, _dp, _ip, _ip]),
     'dbat_hip_debug_ray_angles_host': (C.c_int, [C.POINTER(Problem), _dp, _dp]),
+    'dbat_hip_point_depths': (C.c_int, [_H, _dp, C.c_double, _dp, _dp, C.POINTER(DepthStats)]),
+    'dbat_hip_set_chirality': (C.c_int, [_H, C.c_int32, C.c_double]),
+    'dbat_hip_chirality_stats': (C.c_int, [_H, C.POINTER(VetoStats)]),
     'dbat_hip_coverage': (C.c_int, [_H, _dp, _dp, _dp, _lp, _dp, _lp, _lp]),
     'dbat_hip_residual_stats': (C.c_int, [_H, _dp, _lp, _dp, _lp, _dp, _dp, _dp, _lp]),
     'dbat_hip_quality_hull_cap': (C.c_int32, []),
@@ -194,6 +205,8 @@ DEBUG_SYMBOLS = {
                                                  _dp, _dp, _dp, _dp, _dp, _dp]),
     'dbat_hip_debug_ray_angles_ms': (C.c_int, [_H, _dp, C.POINTER(C.c_int64)]),
     'dbat_hip_debug_quality_ms': (C.c_int, [_H, _dp]),
+    'dbat_hip_debug_point_depths_ms': (C.c_int, [_H, _dp]),
+    'dbat_hip_debug_chirality_pass_ms': (C.c_int, [_H, _dp, C.c_int32, _dp]),
 }
 
 _lib = None
@@ -633,6 +646,44 @@ class Handle:
         return dict(points=float(ms[0]), cam_dirs=float(ms[1]), cam_pairs=float(ms[2]), mfma=int(info[0]),
                     workgroups=int(info[1]))
 
+    def point_depths(self, x, thr=0.0, want_depth=True):
+        """Point depths at x (dbat_hip_point_depths): (depth, image_min, n_behind, min_depth, argmin) -- the depth of
+        every IP column (None with want_depth=False), the smallest depth per image (NaN for none), the number of
+        columns with !(depth > thr), the smallest depth and the smallest column that attains it (-1: none)."""
+        x = np.ascontiguousarray(x, float)
+        nc, no = int(self.prob.n_images), int(self.prob.n_obs)
+        d = np.zeros(max(no, 1)) if want_depth else None
+        im = np.zeros(max(nc, 1))
+        st = DepthStats()
+        check(self.lib.dbat_hip_point_depths(self.h, dptr(x), float(thr), dptr(d), dptr(im), C.byref(st)))
+        return (d[:no] if want_depth else None), im[:nc], int(st.n_behind), float(st.min_depth), int(st.argmin_column)
+
+    def point_depths_ms(self):
+        """Device-event milliseconds of the kernels of the last point_depths (debug)."""
+        ms = np.zeros(1)
+        check(self.lib.dbat_hip_debug_point_depths_ms(self.h, dptr(ms)))
+        return float(ms[0])
+
+    def chirality_pass_ms(self, x, reps=20):
+        """Device-event milliseconds of one pass of the built-in veto at x (debug; the mean of reps passes back to back)
+        and the count it found."""
+        x = np.ascontiguousarray(x, float)
+        ms = np.zeros(2)
+        check(self.lib.dbat_hip_debug_chirality_pass_ms(self.h, dptr(x), int(reps), dptr(ms)))
+        return float(ms[0]), int(ms[1])
+
+    def set_chirality(self, on=True, min_depth=0.0):
+        """The built-in chirality veto of the damping loops (dbat_hip_set_chirality): a trial point with an observation
+        whose depth is not above min_depth is rejected.  DbatHipError for a shard of several or a min_depth that is
+        not finite."""
+        check(self.lib.dbat_hip_set_chirality(self.h, int(bool(on)), float(min_depth)))
+
+    def chirality_stats(self):
+        """(tested, rejected, n_behind, min_depth) of the built-in veto during the last solve."""
+        st = VetoStats()
+        check(self.lib.dbat_hip_chirality_stats(self.h, C.byref(st)))
+        return int(st.tested), int(st.rejected), int(st.n_behind), float(st.min_depth)
+
     def coverage(self):
         """Image coverage by the measured points (dbat_hip_coverage), per image: a dict with lo, hi (2, nImages), rad_max
         [mm], rad_ip, hull_area [px^2] and hull, the list of the hulls' vertices as arrays of IP columns
@@ -772,6 +823,7 @@ def release(h, keep=True):
     if _cached is not None and _cached is not h:
         _cached.close()
     h.set_deterministic(False)
+    h.set_chirality(False)
     _cached = h
 
 

@@ -26,6 +26,7 @@
 #include "resect.hpp"
 #include "robust.hpp"
 #include "angles.hpp"
+#include "depth.hpp"
 #include "quality.hpp"
 
 namespace dbat {
@@ -1350,6 +1351,104 @@ struct Core {
             ang.ms[i] = t;
         }
     }
+    // camera-major slot of every owned observation (processing order): the plan's stable counting sort by camera, tiled
+    // part first
+    std::vector<int32_t> cm_slots() const {
+        std::vector<int32_t> cmm((size_t)nobs);
+        const int64_t ntiled = P.nb_tiled > 0 ? P.batch_start[P.nb_tiled] : 0;
+        std::vector<int64_t> cnt((size_t)P.nc + 1);
+        for (int part = 0; part < 2; ++part) {
+            const int64_t lo = part ? ntiled : 0, hi = part ? nobs : ntiled;
+            std::fill(cnt.begin(), cnt.end(), 0);
+            for (int64_t o = lo; o < hi; ++o) ++cnt[P.o_cam[o] + 1];
+            for (int c = 0; c < P.nc; ++c) cnt[c + 1] += cnt[c];
+            for (int64_t o = lo; o < hi; ++o) cmm[o] = (int32_t)(lo + cnt[P.o_cam[o]]++);
+        }
+        return cmm;
+    }
+    // ---- point depths and the chirality veto at zt (depth.hpp).  What the kernels need beyond the plan's uploads -- the
+    // IP column of every slot of the camera-major copy, the scratch of the reductions, the depths in IP-column order --
+    // is built by the first call (or by set_chirality) and kept: no allocation per call, none inside a damping loop.
+    // The camera records are cams_f, the ones eval_f / eval_f_step leave at the point they evaluated.
+    struct DepthPlan {
+        bool ready = false;
+        DevBuf<int64_t> cm_col;
+        DevBuf<long long> chunk_col;
+        DevBuf<unsigned long long> red;                  // [0] count, [1] smallest key, [2, 2 + nc) per image, then per chunk
+        DevBuf<double> depth;
+        std::vector<unsigned long long> img_host;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        double ms = 0;                                   // last point_depths: reset of the scratch + the two kernels
+        ~DepthPlan() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+    } dep;
+    static constexpr int DEPTH_SLOT = 52;                // mailbox slots 52..54: no other kernel writes them
+    void depth_plan() {
+        if (dep.ready) return;
+        std::vector<int64_t> col((size_t)std::max<int64_t>(nobs, 1), 0);
+        const std::vector<int32_t> cmm = cm_slots();
+        for (int64_t o = 0; o < nobs; ++o) col[(size_t)cmm[o]] = P.o_row[o];
+        dep.cm_col.upload(col);
+        dep.chunk_col.alloc((size_t)std::max<int64_t>(n_cm_chunks_all, 1));
+        dep.red.alloc((size_t)(2 + std::max(P.nc, 1) + std::max<int64_t>(n_cm_chunks_all, 1)));
+        dep.depth.alloc((size_t)std::max<int64_t>(P.no, 1));
+        dep.img_host.resize((size_t)std::max(P.nc, 1));
+        for (auto &e : dep.ev) HIPCHK(hipEventCreate(&e));
+        dep.ready = true;
+    }
+    // the depth kernels at zz with the camera records cams_f; FULL: depths, per-image minima and the argmin as well.
+    // Results: the mailbox (hpin[DEPTH_SLOT ..]) once the stream has run (ticket mb_seq).
+    template <bool FULL>
+    void depth_enqueue(const double *zz, double thr, bool want_depth) {
+        HIPCHK(hipMemsetAsync(dep.red.p, 0, sizeof(unsigned long long), stream));
+        HIPCHK(hipMemsetAsync(dep.red.p + 1, 0xFF, (size_t)(FULL ? 1 + P.nc : 1) * sizeof(unsigned long long), stream));
+        unsigned long long *img = dep.red.p + 2, *ckey = dep.red.p + 2 + std::max(P.nc, 1);
+        if (n_cm_chunks_all > 0)
+            launch<k_depth_cm<FULL>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, zz, (int64_t)P.NS, (const CamRec *)cams_f.p, (const int32_t *)cm_pt.p,
+                                     (const int32_t *)cm_chunk_cam.p, (const int64_t *)cm_chunk_start.p, (const int64_t *)dep.cm_col.p, thr,
+                                     want_depth ? dep.depth.p : (double *)nullptr, dep.red.p, img, ckey, dep.chunk_col.p);
+        launch<k_depth_finish<FULL>>(dim3(1), dim3(256), 0, n_cm_chunks_all, (const unsigned long long *)dep.red.p, (const unsigned long long *)ckey,
+                                     (const long long *)dep.chunk_col.p, hpin, DEPTH_SLOT, ++mb_seq);
+    }
+    static int64_t mailbox_int(const double *slot) { int64_t v; memcpy(&v, slot, sizeof v); return v; }
+    void point_depths(double thr, double *hdepth, double *himg, int64_t &n_behind, double &min_depth, int64_t &argmin) {
+        depth_plan();
+        prep_cams(zt.p, cams_f.p);
+        HIPCHK(hipEventRecord(dep.ev[0], stream));
+        depth_enqueue<true>(zt.p, thr, hdepth != nullptr);
+        HIPCHK(hipEventRecord(dep.ev[1], stream));
+        if (hdepth && P.no > 0) HIPCHK(hipMemcpyAsync(hdepth, dep.depth.p, (size_t)P.no * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (himg && P.nc > 0)
+            HIPCHK(hipMemcpyAsync(dep.img_host.data(), dep.red.p + 2, (size_t)P.nc * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        sync();                                          // (not armed: the copies behind the ticket are waited for too)
+        if (himg) for (int c = 0; c < P.nc; ++c) himg[c] = depth_from_key(dep.img_host[c]);
+        n_behind = mailbox_int(hpin + DEPTH_SLOT); min_depth = hpin[DEPTH_SLOT + 1]; argmin = mailbox_int(hpin + DEPTH_SLOT + 2);
+        float t = 0;
+        HIPCHK(hipEventElapsedTime(&t, dep.ev[0], dep.ev[1]));
+        dep.ms = t;
+    }
+    // The built-in chirality veto (dbat_hip_set_chirality): at every trial point a damping loop consults its veto at,
+    // the number of observations with !(depth > chir_thr) at zt; a non-zero count rejects.  Two words cross to the host
+    // (the count and the smallest depth, kept for dbat_hip_chirality_stats), the parameter vector never does.
+    bool chirality = false;
+    double chir_thr = 0.0;
+    int64_t veto_tested = 0, veto_rejected = 0, veto_n_behind = 0;
+    double veto_min_depth = NAN;
+    void set_chirality(bool on, double thr) {
+        if (on) depth_plan();
+        chirality = on; chir_thr = thr;
+    }
+    void veto_stats_reset() { veto_tested = veto_rejected = veto_n_behind = 0; veto_min_depth = NAN; }
+    bool chirality_veto() {                              // right after eval_f_step: cams_f are the trial point's records
+        stage(3);
+        depth_enqueue<false>(zt.p, chir_thr, false);
+        mb_armed = true;
+        sync();
+        const int64_t nb = mailbox_int(hpin + DEPTH_SLOT);
+        ++veto_tested;
+        if (nb == 0) return false;
+        ++veto_rejected; veto_n_behind = nb; veto_min_depth = hpin[DEPTH_SLOT + 1];
+        return true;
+    }
     // ---- image coverage and marking-residual statistics (quality.hpp).  Built by the first call and kept, as the
     // angles' plan: the columns of every image (IP is image-major), where every point's observations start, the
     // measured pixel coordinates in IP order (the observations are structure: dbat_hip_set_values never changes them;
@@ -1513,19 +1612,7 @@ struct Core {
         } else if (nobs > 0) {
             HIPCHK(hipMemcpyAsync(o_w_base.p, o_w.p, (size_t)2 * nobs * sizeof(double), hipMemcpyDeviceToDevice, stream));
         }
-        {   // camera-major slot of every observation: the plan's stable counting sort by camera, tiled part first
-            std::vector<int32_t> cmm((size_t)nobs);
-            const int64_t ntiled = P.nb_tiled > 0 ? P.batch_start[P.nb_tiled] : 0;
-            std::vector<int64_t> cnt((size_t)P.nc + 1);
-            for (int part = 0; part < 2; ++part) {
-                const int64_t lo = part ? ntiled : 0, hi = part ? nobs : ntiled;
-                std::fill(cnt.begin(), cnt.end(), 0);
-                for (int64_t o = lo; o < hi; ++o) ++cnt[P.o_cam[o] + 1];
-                for (int c = 0; c < P.nc; ++c) cnt[c + 1] += cnt[c];
-                for (int64_t o = lo; o < hi; ++o) cmm[o] = (int32_t)(lo + cnt[P.o_cam[o]]++);
-            }
-            cm_map.upload(cmm);
-        }
+        cm_map.upload(cm_slots());
         if (use_sig) {   // slot-major slot: group g, slot j, point i at obs0_g + j*m_g + i (plan.hpp, signature groups)
             std::vector<int32_t> sgm((size_t)nobs, -1);
             for (size_t q = 0; q < P.sg_chunk.size() / 8; ++q) {
@@ -1713,12 +1800,13 @@ static bool term_fun(Core &c, const dbat_hip_options &o, double JpJp, double f, 
     if (o.abs_term) return nr <= o.conv_tol;
     return std::sqrt(JpJp) <= o.conv_tol * nr;
 }
-// vetoFun(t) at the trial point c.zt
+// vetoFun(t) at the trial point c.zt, right after eval_f_step has evaluated it
 static bool vetoed(Core &c, const dbat_hip_options &o) {
-    if (!o.veto_fun) return false;
+    const bool behind = c.chirality && c.chirality_veto();       // the built-in veto (dbat_hip_set_chirality): on the device
+    if (!o.veto_fun) return behind;
     std::vector<double> x((size_t)c.P.n);
     c.z_to_x(c.zt.p, x.data());
-    return o.veto_fun(o.veto_user, x.data(), c.P.n) != 0;
+    return (o.veto_fun(o.veto_user, x.data(), c.P.n) != 0) || behind;      // (either one rejects; the caller's is always asked)
 }
 
 // the line the lsa solver prints with 'trace', handed to the caller while the loop runs (dbat_hip_trace_fn)
@@ -2477,6 +2565,7 @@ namespace dbat {
 static void solve_once(Core &c, const dbat_hip_options *opt, double *x, dbat_hip_result *result, double *res, double *damp,
                        double *aux, double *trace) {
     c.n_res_evals = c.n_lin = c.n_solves = c.n_trace_only = 0;
+    c.veto_stats_reset();
     c.trace_begin();
     c.x_to_z(x, c.z.p);
     c.lambda_lin = NAN;
@@ -2627,6 +2716,7 @@ int dbat_hip_solve_robust(dbat_hip_handle *h, const dbat_hip_options *opt, const
     if (!rr) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
     if (const char *e = robust_args_error(ropt)) { g_err = e; return DBAT_HIP_EINVAL; }
     Core &c = *h->core;
+    if (c.chirality) { g_err = "robust solve: the chirality veto (dbat_hip_set_chirality) is not combined with the reweighting loop"; return DBAT_HIP_EUNSUPPORTED; }
     DeviceGuard dev_guard(c.device);
     memset(rr, 0, sizeof *rr);
     auto t0 = std::chrono::steady_clock::now();
@@ -2836,6 +2926,76 @@ int dbat_hip_ray_angles(dbat_hip_handle *h, const double *x, double *op_angle, d
     c.ray_angles(op_angle, cam_angle, op_rays, cam_rays);
     return DBAT_HIP_OK;
     API_CATCH
+}
+
+static bool depth_one_rank(const Core &c, const char *what) {
+    if (c.P.nranks <= 1) return true;
+    g_err = std::string(what) + ": this handle is one shard of " + std::to_string(c.P.nranks) +
+            " (the counts and minima of the shards are not combined; use a handle of the whole problem)";
+    return false;
+}
+
+int dbat_hip_point_depths(dbat_hip_handle *h, const double *x, double thr, double *depth_out, double *img_min_out,
+                          dbat_hip_depth_stats *stats_out) {
+    API_TRY
+    if (!h || !x || !stats_out) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    if (thr != thr) { g_err = "point depths: the threshold is NaN"; return DBAT_HIP_EINVAL; }
+    Core &c = *h->core;
+    if (!depth_one_rank(c, "point depths")) return DBAT_HIP_EUNSUPPORTED;
+    DeviceGuard dev_guard(c.device);
+    c.x_to_z(x, c.zt.p);
+    c.point_depths(thr, depth_out, img_min_out, stats_out->n_behind, stats_out->min_depth, stats_out->argmin_column);
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+int dbat_hip_set_chirality(dbat_hip_handle *h, int32_t on, double min_depth) {
+    API_TRY
+    if (!h) { g_err = "null handle"; return DBAT_HIP_EINVAL; }
+    if (!std::isfinite(min_depth)) { g_err = "chirality veto: min_depth must be finite"; return DBAT_HIP_EINVAL; }
+    Core &c = *h->core;
+    if (on && !depth_one_rank(c, "chirality veto")) return DBAT_HIP_EUNSUPPORTED;
+    DeviceGuard dev_guard(c.device);
+    c.set_chirality(on != 0, min_depth);
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+int dbat_hip_chirality_stats(const dbat_hip_handle *h, dbat_hip_veto_stats *out) {
+    if (!h || !out) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    const Core &c = *h->core;
+    out->tested = c.veto_tested; out->rejected = c.veto_rejected; out->n_behind = c.veto_n_behind; out->min_depth = c.veto_min_depth;
+    return DBAT_HIP_OK;
+}
+
+/* Debug / measurement: the veto's own pass (the reset of its two words, k_depth_cm<false>, k_depth_finish<false>) at x,
+ * reps times back to back between two device events: ms[0] = milliseconds per pass, ms[1] = the count it found. */
+int dbat_hip_debug_chirality_pass_ms(dbat_hip_handle *h, const double *x, int32_t reps, double *ms) {
+    API_TRY
+    if (!h || !x || !ms || reps < 1) { g_err = "bad argument"; return DBAT_HIP_EINVAL; }
+    Core &c = *h->core;
+    if (!depth_one_rank(c, "chirality veto")) return DBAT_HIP_EUNSUPPORTED;
+    DeviceGuard dev_guard(c.device);
+    c.depth_plan();
+    c.x_to_z(x, c.zt.p);
+    c.prep_cams(c.zt.p, c.cams_f.p);
+    HIPCHK(hipEventRecord(c.dep.ev[0], c.stream));
+    for (int i = 0; i < reps; ++i) c.depth_enqueue<false>(c.zt.p, c.chir_thr, false);
+    HIPCHK(hipEventRecord(c.dep.ev[1], c.stream));
+    c.sync();
+    float t = 0;
+    HIPCHK(hipEventElapsedTime(&t, c.dep.ev[0], c.dep.ev[1]));
+    ms[0] = t / reps; ms[1] = (double)Core::mailbox_int(c.hpin + Core::DEPTH_SLOT);
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+/* Debug / measurement: milliseconds of the kernels of the last dbat_hip_point_depths on the handle's stream (device
+ * events: the reset of the scratch, k_depth_cm, k_depth_finish). */
+int dbat_hip_debug_point_depths_ms(dbat_hip_handle *h, double *ms) {
+    if (!h || !ms || !h->core->dep.ready) { g_err = "no point depths computed on this handle"; return DBAT_HIP_EINVAL; }
+    ms[0] = h->core->dep.ms;
+    return DBAT_HIP_OK;
 }
 
 /* Debug / measurement: milliseconds of the last dbat_hip_ray_angles on the handle's stream (device events): ms[0] the

@@ -102,7 +102,7 @@ def _robust_args(robust, robust_k, robust_scale, robust_max_outer, robust_tol):
 
 def bundle(s, *args, device=None, comm=None, store_trace=True, jacobian=False, deterministic=False,
            term_fun=None, veto_fun=None, reuse_handle=True, robust=None, robust_k=None, robust_scale='apriori',
-           robust_max_outer=10, robust_tol=1e-3):
+           robust_max_outer=10, robust_tol=1e-3, min_depth=0.0):
     """[s,ok,iters,s0,E] = bundle(s[,maxIter][,damping][,'trace'][,tol]
     [,'absterm'][,'singulartest'|'nosingulartest'][,veto][,'pmdof'][,'dofverb'])
 
@@ -117,6 +117,13 @@ def bundle(s, *args, device=None, comm=None, store_trace=True, jacobian=False, d
     the two function handles of the reference's solver interface, for callers that used the solvers directly.
     `reuse_handle=False` builds (and destroys) a handle of its own instead of using the cached one (_hip.acquire).
     The returned struct shares the arrays bundle() does not change (IP.*, masks, blocks) with its input.
+
+    The logical `veto` argument turns the chirality veto on (bundle.m:125-127; the reference's own `chirality` is
+    undefined, bundle.m:169): the damping loops reject a trial point at which some object point is not in front of a
+    camera that sees it -- depth <= `min_depth`, the depths of point_depths() -- with the consequences of a veto_fun
+    that returns true.  The test runs on the device (dbat_hip_set_chirality).  E.chirality is then True and E.veto holds
+    tested, rejected (trial points) and n_behind, min_depth of the last rejected one.  'gm' has no trial points.  Not
+    with `comm` of several ranks, not with `robust=`.
 
     Robust estimation (iteratively reweighted least squares over the image points, dbat_hip_solve_robust):
     `robust='huber' | 'cauchy'` down-weights image points with large residuals.  Per outer step the weight factor
@@ -133,10 +140,16 @@ def bundle(s, *args, device=None, comm=None, store_trace=True, jacobian=False, d
     if ro is not None and (term_fun is not None or veto_fun is not None):
         raise BadInput('bundle: robust=... takes no term_fun / veto_fun')
     o = _parse_args(args)
+    if (isinstance(min_depth, bool) or not isinstance(min_depth, (int, float, np.integer, np.floating))
+            or not np.isfinite(min_depth)):
+        raise BadInput('bundle: min_depth must be a finite number, not %r' % (min_depth,))
     if o['veto']:
-        # bundle.m:169 references an undefined function `chirality`
-        # (SURVEY Appendix B item 2): the reference errors at this point too.
-        raise BadInput("chirality veto is not defined in the reference (bundle.m:169)")
+        # bundle.m:169 references an undefined function `chirality`; here: every point in
+        # front of every camera that sees it, tested on the device
+        if ro is not None:
+            raise BadInput('bundle: the chirality veto is not combined with robust=...')
+        if comm is not None and comm.world_size > 1:
+            raise BadInput('bundle: the chirality veto runs on one-rank handles only (comm with %d ranks)' % comm.world_size)
     s = share_struct(s)          # (namespaces copied, arrays shared: nothing below writes into an array of the input)
     # bundle.m:137-154: a fixed parameter cannot be used as a prior observation
     for nm in ('IO', 'EO', 'OP'):
@@ -165,6 +178,8 @@ def bundle(s, *args, device=None, comm=None, store_trace=True, jacobian=False, d
     try:
         if deterministic:                                            # fixed-order sums: bit-identical runs (parity mode)
             h.set_deterministic(True)
+        if world == 1:
+            h.set_chirality(o['veto'], float(min_depth))             # (every call: a cached handle keeps no setting)
         if comm is not None and world > 1:
             if hasattr(comm, 'attach'):
                 comm.attach(h)                                       # RCCL communicator inside the library
@@ -186,7 +201,9 @@ def bundle(s, *args, device=None, comm=None, store_trace=True, jacobian=False, d
             x, res, rr, damp, aux, T, rres, omega = h.solve_robust(x0, opt, ropt)
         t_host.append(time.perf_counter())
         E = NS(maxIter=o['maxIter'], convTol=o['convTol'], absTerm=o['absTerm'],
-               singularTest=o['singularTest'], chirality=False)
+               singularTest=o['singularTest'], chirality=o['veto'], veto=None)
+        if o['veto']:
+            E.veto = NS(**dict(zip(('tested', 'rejected', 'n_behind', 'min_depth'), h.chirality_stats())))
         name = 'gm' if o['damping'] in ('none', 'gm') else o['damping']
         if name == 'gm':
             E.damping = NS(name='gm')
@@ -526,6 +543,27 @@ def ray_angles(s, E=None, device=0):
     finally:
         _hip.release(h, keep=done)
     return NS(op=op, cam=cam, op_rays=op_rays, cam_rays=cam_rays)
+
+
+def point_depths(s, E=None, device=0):
+    """Depth of every object point with respect to every camera that sees it, from the device (dbat_hip_point_depths) on
+    the handle bundle() left behind -- photogrammetry/pm_multidepth.m with pointdepth.m / ptdepth.m, sign chosen so
+    that a point in front of the camera has a positive depth.  Evaluated at the values in s (E is accepted so that the
+    call reads like ray_angles').  Fields:
+      depth      (nObs,) depth of every IP column
+      n_behind   IP columns with !(depth > 0): a NaN depth counts        behind  those columns, ascending
+      min_depth  smallest depth (NaN if none is a number)                argmin  smallest IP column that attains it (-1)
+      image_min  (nImages,) smallest depth per image, NaN for an image without points
+    This is what the chirality veto of bundle(s, True) tests at every trial point."""
+    h = _hip.acquire(s, device)
+    done = False
+    try:
+        depth, image_min, n_behind, min_depth, argmin = h.point_depths(h.serialize(), 0.0)
+        done = True
+    finally:
+        _hip.release(h, keep=done)
+    return NS(depth=depth, n_behind=n_behind, behind=np.flatnonzero(~(depth > 0)), min_depth=min_depth, argmin=argmin,
+              image_min=image_min)
 
 
 def _corner_radius(s, i):

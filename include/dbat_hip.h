@@ -500,6 +500,44 @@ int  dbat_hip_ray_angles(dbat_hip_handle *h, const double *x, double *op_angle, 
  * ip_pt), for tests of the definition; never on the product path.  Either output may be NULL. */
 int  dbat_hip_debug_ray_angles_host(const dbat_hip_problem *prob, double *op_angle, double *cam_angle);
 
+/* Point depths at x (additive to ABI 5): the depth of every object point with respect to every camera that sees it,
+ * d_k = -M'_(3,:) (Q_pt(k) - q0_cam(k)) for IP column k, M' the world-to-camera rotation and q0 the camera centre --
+ * -ptdepth(P, X) of photogrammetry/pm_multidepth.m:19-37 (pointdepth.m, ptdepth.m) with P = K M' [I, -q0]; positive
+ * in front of the camera.  Every IP column counts.
+ *   x            the parameter vector (as for dbat_hip_ray_angles; fixed values come from the handle)
+ *   thr          an observation is "behind" when !(d_k > thr); a NaN depth therefore counts as behind.  Not NaN.
+ *   depth_out    [n_obs] depths in IP-column order, or NULL
+ *   img_min_out  [n_images] smallest depth of every image, NaN for an image without points, or NULL
+ *   stats_out    n_behind; min_depth, the smallest depth that is a number (NaN if there is none); argmin_column, the
+ *                smallest IP column that attains it (-1 if there is none)
+ * One pass over the plan's camera-major copy (csrc/depth.hpp); counts and minima are reduced with integer atomics
+ * only, so two calls give the same bits.  Scratch is kept on the handle.  A handle that is one shard of several
+ * (shard_count > 1) returns DBAT_HIP_EUNSUPPORTED. */
+typedef struct dbat_hip_depth_stats {
+    int64_t n_behind;
+    double  min_depth;
+    int64_t argmin_column;
+} dbat_hip_depth_stats;
+int  dbat_hip_point_depths(dbat_hip_handle *h, const double *x, double thr, double *depth_out, double *img_min_out,
+                           dbat_hip_depth_stats *stats_out);
+
+/* The chirality veto of bundle.m:125-127,168-172 (a handle setting, like dbat_hip_set_deterministic): on != 0 makes the
+ * damping loops of every later dbat_hip_solve reject a trial point at which an observation has !(depth > min_depth) --
+ * at exactly the places where they consult dbat_hip_options.veto_fun (gauss_newton_armijo.m:268-271,
+ * levenberg_marquardt.m:170-173, levenberg_marquardt_powell.m:146-166), with the same consequences; with a veto_fun
+ * as well, either one rejects.  The test runs on the device-resident trial point: two words come back, the parameter
+ * vector never leaves the device.  Gauss-Markov (damping 0) has no trial points and ignores the setting.  min_depth
+ * must be finite (DBAT_HIP_EINVAL); 0 is the reference's meaning of "in front".  DBAT_HIP_EUNSUPPORTED on a handle
+ * that is one shard of several; dbat_hip_solve_robust returns DBAT_HIP_EUNSUPPORTED while the setting is on. */
+int  dbat_hip_set_chirality(dbat_hip_handle *h, int32_t on, double min_depth);
+/* The built-in veto during the last dbat_hip_solve: trial points tested, trial points rejected, and n_behind /
+ * min_depth of the last rejected one (0 / NaN if none was). */
+typedef struct dbat_hip_veto_stats {
+    int64_t tested, rejected, n_behind;
+    double  min_depth;
+} dbat_hip_veto_stats;
+int  dbat_hip_chirality_stats(const dbat_hip_handle *h, dbat_hip_veto_stats *out);
+
 /* Image coverage by the measured points (photogrammetry/coverage.m:113-185), per image, from the pixel coordinates
  * alone (no x).  Image c owns the IP columns of its points (IP is image-major); every index below is an IP column.
  *   lo, hi      [2*n_images] exact min and max of u and v; NaN for an image without points
