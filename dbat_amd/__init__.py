@@ -7,6 +7,8 @@ Host-side mirror of the reference's interface for the bundle hot path:
                  ray_angles(s, E): intersection angles of every object point and every image, ray counts
                  point_depths(s, E): depth of every object point in every camera that sees it (the chirality veto's test)
                  network_quality(s, E): image coverage and marking-residual statistics, on the device
+                 rigidalign, multixform, multialign: misc/rigidalign.m, pm_multixform.m, pm_multialign.m on the device;
+                 transform_network(s, T), align_network(s, ref_OP): a whole struct into another coordinate system
     loadpm       PhotoModeler export loader (known-answer fixtures)
     initial      resect / forwintersect: initial EO and OP (photogrammetry/resect.m, forwintersect.m)
     report       the result file (bundle_result_file.m)
@@ -16,3 +18,4 @@ Host-side mirror of the reference's interface for the bundle hot path:
 """
 from .dbatstruct import make_struct, seteoest_depend, validate  # noqa: F401
 from .driver import bundle, bundle_cov, bundle_reliability, ray_angles, point_depths, network_quality, BadInput  # noqa: F401
+from .driver import rigidalign, multixform, multialign, transform_network, align_network  # noqa: F401

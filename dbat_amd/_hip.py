@@ -172,6 +172,8 @@ SYMBOLS = {
     'dbat_hip_owned_mask': (C.c_int, [_H, _bp]),
     'dbat_hip_forwintersect': (C.c_int, [_H, _dp, _bp, _dp]),
     'dbat_hip_resect': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp]),
+    'dbat_hip_rigidalign': (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _bp, C.c_int32, _dp, _dp, _dp]),
+    'dbat_hip_multixform': (C.c_int, [C.c_int32, _dp, C.c_int64, C.c_int32, _dp, C.c_int64, _dp, _bp]),
     'dbat_hip_bench_step': (C.c_int, [_H, C.c_double, C.c_int32, _dp]),
     'dbat_hip_structure_key': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_uint64)]),
     'dbat_hip_handle_key': (C.c_int, [_H, C.POINTER(C.c_uint64)]),
@@ -207,6 +209,8 @@ DEBUG_SYMBOLS = {
     'dbat_hip_debug_quality_ms': (C.c_int, [_H, _dp]),
     'dbat_hip_debug_point_depths_ms': (C.c_int, [_H, _dp]),
     'dbat_hip_debug_chirality_pass_ms': (C.c_int, [_H, _dp, C.c_int32, _dp]),
+    'dbat_hip_debug_align_ms': (C.c_int, [_dp]),
+    'dbat_hip_debug_align_timing': (C.c_int, [C.c_int32]),
 }
 
 _lib = None
@@ -895,6 +899,61 @@ def resect_poses(pt_start, X, xn, tri_start, tri, device=0):
     check(lib.dbat_hip_resect(int(device), n, ps.ctypes.data_as(i64p), dptr(Xf), dptr(xf), ts.ctypes.data_as(i64p),
                               tf.ctypes.data_as(_ip), dptr(P), dptr(rms)))
     return P.reshape(n, 4, 3).transpose(0, 2, 1), rms
+
+
+def rigidalign(X, Y, scale=False, use=None, resid=False, device=0):
+    """dbat_hip_rigidalign over 3-by-n X and Y: (T (4, 4), stats, resid) with stats = dict(alpha, rms, used, sv_ratio) and
+    resid 3-by-n (NaN in the columns that are not used) or None."""
+    lib = load()
+    X, Y = np.asarray(X, float), np.asarray(Y, float)
+    if X.ndim != 2 or X.shape[0] != 3 or X.shape != Y.shape:
+        raise ValueError('rigidalign: X and Y must both be 3-by-n')
+    n = X.shape[1]
+    Xf, Yf = _f64(X), _f64(Y)
+    u = None
+    if use is not None:
+        u = np.ascontiguousarray(np.asarray(use, bool).ravel()).view(np.uint8)
+        if u.shape[0] != n:
+            raise ValueError('rigidalign: use must have one entry per column')
+    T, st = np.zeros(16), np.zeros(4)
+    r = np.empty(3 * n) if resid else None
+    check(lib.dbat_hip_rigidalign(int(device), n, dptr(Xf), dptr(Yf), None if u is None else u.ctypes.data_as(_bp),
+                                  int(bool(scale)), dptr(T), dptr(st), dptr(r)))
+    return (T.reshape(4, 4, order='F'), dict(alpha=float(st[0]), rms=float(st[1]), used=int(st[2]), sv_ratio=float(st[3])),
+            None if r is None else r.reshape(3, n, order='F'))
+
+
+def multixform(EO, OP, T, device=0):
+    """dbat_hip_multixform: (EO, OP, fail) -- new column-major arrays of the shapes given (EO with six rows or more, the
+    rows from the seventh on copied) and the per-camera failure flags."""
+    lib = load()
+    EO, OP, T = np.asarray(EO, float), np.asarray(OP, float), np.asarray(T, float)
+    if T.shape != (4, 4):
+        raise ValueError('multixform: T must be 4-by-4')
+    EO = np.zeros((6, 0)) if EO.size == 0 else EO
+    OP = np.zeros((3, 0)) if OP.size == 0 else OP
+    if EO.ndim != 2 or OP.ndim != 2 or (OP.size and OP.shape[0] != 3):
+        raise ValueError('multixform: EO must be 6-by-M (or more rows), OP 3-by-N')
+    nc, npnt = (EO.shape[1] if EO.size else 0), (OP.shape[1] if OP.size else 0)
+    rows = EO.shape[0] if nc else 6
+    eo, op = np.array(EO, float, order='F'), np.array(OP, float, order='F')
+    fail = np.zeros(max(nc, 1), np.uint8)
+    check(lib.dbat_hip_multixform(int(device), dptr(_f64(T)), nc, int(rows), dptr(eo.reshape(-1, order='F')) if nc else None,
+                                  npnt, dptr(op.reshape(-1, order='F')) if npnt else None, fail.ctypes.data_as(_bp)))
+    return eo, op, fail[:nc].astype(bool)
+
+
+def align_timing(on=True):
+    """Device events around the kernels of rigidalign / multixform calls on this thread (debug; off by default)."""
+    check(load().dbat_hip_debug_align_timing(int(bool(on))))
+
+
+def align_ms():
+    """Device-event milliseconds of the kernels of the last rigidalign / multixform call on this thread, after
+    align_timing(True) (debug)."""
+    ms = np.zeros(5)
+    check(load().dbat_hip_debug_align_ms(dptr(ms)))
+    return dict(centroid=float(ms[0]), cross=float(ms[1]), resid=float(ms[2]), points=float(ms[3]), cams=float(ms[4]))
 
 
 def plan_layout_stats(s, shard_rank=0, shard_count=1):

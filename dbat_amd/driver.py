@@ -663,6 +663,119 @@ def network_quality(s, E=None, device=0):
     return NS(coverage=c, coverage_union=coverage_union, residuals=res)
 
 
+def _call(fn, *a, **kw):
+    """fn(*a, **kw) with the library's DBAT_HIP_EINVAL, and the binding's complaints about shapes, as BadInput."""
+    try:
+        return fn(*a, **kw)
+    except _hip.DbatHipError as e:
+        if e.code == _hip.EINVAL:
+            raise BadInput(str(e)) from e
+        raise
+    except ValueError as e:
+        raise BadInput(str(e)) from e
+
+
+def rigidalign(X, Y, scale=False, use=None, device=0):
+    """[T,R,d,alpha] = rigidalign(X, Y, scale) (misc/rigidalign.m) for 3-by-n point sets, the sums on the device
+    (dbat_hip_rigidalign): the rigid-body (scale=False: alpha = 1) or similarity transformation that minimises
+    sum |alpha R x_i + d - y_i|^2, T = [alpha R, d; 0 0 0 1].  `use` (n booleans) restricts the sum to some columns;
+    the others may hold anything.  BadInput for fewer than three used columns, a used column that is not finite, and
+    points that are collinear (rigidalign.m returns an arbitrary rotation for those)."""
+    T, st, _ = _call(_hip.rigidalign, X, Y, scale, use=use, device=device)
+    alpha = st['alpha']
+    return T, T[:3, :3] / alpha, T[:3, 3].copy(), alpha
+
+
+def multixform(EO, OP, T, device=0):
+    """[EO,OP,fail] = pm_multixform(EO, OP, T) (photogrammetry/pm_multixform.m) on the device (dbat_hip_multixform): the
+    similarity T applied to the object points OP (3-by-N) and the camera stations EO (6- or 7-by-M: centre, omega, phi,
+    kappa; rows from the seventh on are left as they are).  Either array may be empty.  fail (M booleans) marks the
+    cameras whose values are not finite; they stay as they are.  The angles are those of the rotation M' R' -- the
+    reference takes them from M' R' / alpha.  BadInput for a T that is not a similarity."""
+    return _call(_hip.multixform, EO, OP, T, device=device)
+
+
+def multialign(EO, OP, i, ra=0.0, device=0):
+    """[EO,OP,T] = pm_multialign(EO, OP, i, ra) (photogrammetry/pm_multialign.m:19-24): camera i to the origin, looking
+    down the negative z axis with roll angle ra, T = [RA' M' [I, -C]; 0 0 0 1] applied through multixform."""
+    from .initial import rotmat3d
+    EO = np.asarray(EO, float)
+    if EO.ndim != 2 or EO.shape[0] < 6 or not 0 <= int(i) < EO.shape[1]:
+        raise BadInput('multialign: EO must be 6-by-M (or 7-by-M) and i one of its columns')
+    T = np.eye(4)
+    T[:3, :3] = rotmat3d([0.0, 0.0, -float(ra)]).T @ rotmat3d(EO[3:6, int(i)])      # RA' M'
+    T[:3, 3] = -T[:3, :3] @ EO[:3, int(i)]
+    EO2, OP2, _ = multixform(EO, OP, T, device=device)
+    return EO2, OP2, T
+
+
+def _similarity_parts(T):
+    T = np.asarray(T, float)
+    if T.shape != (4, 4) or not np.all(np.isfinite(T)):
+        raise BadInput('T must be a finite 4-by-4 matrix')
+    det = np.linalg.det(T[:3, :3])
+    if not det > 0:
+        raise BadInput('T(1:3,1:3) is not a scaled proper rotation')
+    alpha = float(np.cbrt(det))
+    return T, alpha, T[:3, :3] / alpha
+
+
+def transform_network(s, T, device=0):
+    """The network of s in another coordinate system: a struct copy with EO.val[:6] and OP.val transformed by the
+    similarity T (multixform, on the device), prior.OP.val and the position rows of prior.EO.val transformed where
+    their `use` is set, and the prior standard deviations of positions multiplied by the scale alpha of T.  The
+    interior orientation and the image points are untouched (shared with s).
+    BadInput when the rotation of T differs from the identity by more than 1e-12 and either some used prior standard
+    deviation is anisotropic within a column (a column used only in part is) or some angle prior is in use: neither
+    keeps its meaning under a rotation."""
+    T, alpha, R = _similarity_parts(T)
+    pOP, pEO = s.prior.OP, s.prior.EO
+    if np.abs(R - np.eye(3)).max() > 1e-12:
+        if np.any(pEO.use[3:6]):
+            raise BadInput('transform_network: a prior observation of an Euler angle does not keep its meaning under a rotation')
+        for name, use, std in (('OP', pOP.use, pOP.std), ('EO', pEO.use[:3], pEO.std[:3])):
+            some = np.any(use, 0)
+            if np.any(some & ~np.all(use, 0)) or np.any(std[:, some] != std[:1, some]):
+                raise BadInput('transform_network: prior.%s has a column with anisotropic standard deviations; '
+                               'they do not keep their meaning under a rotation' % name)
+    s2 = share_struct(s)
+    eo, op, _ = multixform(s.EO.val, s.OP.val, T, device=device)
+    s2.EO.val, s2.OP.val = eo, op
+    # the prior positions go through the device as points: entries that are not in use (NaN as a rule) are held out
+    npnt = pOP.val.shape[1]
+    pv = np.concatenate([pOP.val, pEO.val[:3]], 1)
+    pu = np.concatenate([pOP.use, pEO.use[:3]], 1)
+    if pu.any():
+        _, q, _ = multixform(np.zeros((6, 0)), np.where(pu, pv, 0.0), T, device=device)
+        pv = np.where(pu, q, pv)
+    s2.prior.OP.val = np.asfortranarray(pv[:, :npnt])
+    s2.prior.OP.std = np.asfortranarray(pOP.std * alpha)
+    ev, es = np.array(pEO.val, float, order='F'), np.array(pEO.std, float, order='F')
+    ev[:3] = pv[:, npnt:]
+    es[:3] *= alpha
+    s2.prior.EO.val, s2.prior.EO.std = ev, es
+    return s2
+
+
+def align_network(s, ref_OP, use=None, scale=True, device=0):
+    """Brings the network of s onto reference coordinates: ref_OP is 3-by-nOP with NaN columns for the points that
+    have none.  The similarity (scale=False: rigid-body transformation) is fitted from s.OP.val to ref_OP over the
+    columns that are finite in both and set in `use` (rigidalign) and applied to the whole struct
+    (transform_network).  Returns (s2, T, fit) with fit.alpha, fit.rms, fit.used, fit.resid (3-by-nOP: alpha R x + d - y,
+    NaN where the column is not used), fit.max and fit.argmax (the largest residual norm and its column)."""
+    ref = np.asarray(ref_OP, float)
+    if ref.shape != s.OP.val.shape:
+        raise BadInput('align_network: ref_OP must be 3-by-nOP')
+    ok = np.all(np.isfinite(s.OP.val), 0) & np.all(np.isfinite(ref), 0)
+    if use is not None:
+        ok &= np.asarray(use, bool).ravel()
+    T, st, resid = _call(_hip.rigidalign, s.OP.val, ref, scale, use=ok, resid=True, device=device)
+    s2 = transform_network(s, T, device=device)
+    nrm = np.where(ok, np.sqrt(np.sum(np.where(ok, resid, 0.0) ** 2, 0)), -1.0)
+    k = int(np.argmax(nrm))
+    return s2, T, NS(alpha=st['alpha'], rms=st['rms'], used=st['used'], resid=resid, max=float(nrm[k]), argmax=k)
+
+
 def _reapply_weights(h, E):
     """A robust bundle's weight factors on an acquired handle (acquire() -> set_values restored the base weights):
     covariance and redundancy then describe the final reweighted system.  Returns E.robust."""

@@ -6,7 +6,7 @@ control points and forward intersection of the object points, on
                    built-ins around it: lens correction, the choice of the triangles, centre / angles from the
                    winning 3 x 4 matrix                                  (photogrammetry/resect.m:42-131)
   forwintersect -> dbat_hip_forwintersect (k_forwintersect)              (photogrammetry/forwintersect.m:19-46)
-  largesttriangle (misc/largesttriangle.m:16-41), derotmat3d (photogrammetry/derotmat3d.m:17-19),
+  largesttriangle (misc/largesttriangle.m:16-41), derotmat3d (photogrammetry/derotmat3d.m:17-19), rotmat3d (its inverse),
   lenscorr1 (bundle/cammodel/pm_multilenscorr1.m:45-69 + pm_lens1.m:36-72), cleareo, clearop (misc/)
 
 The CPU restatements these are tested against live in oracle/initial_oracle.py.
@@ -90,6 +90,14 @@ def derotmat3d(M):
     """omega, phi, kappa of a world-to-camera rotation (derotmat3d.m:17-19)."""
     return np.array([np.arctan2(-M[2, 1], M[2, 2]), np.arcsin(M[2, 0]),
                      np.arctan2(-M[1, 0], M[0, 0])])
+
+def rotmat3d(ang):
+    """World-to-camera rotation M' of omega, phi, kappa (pm_eulerrotmat: the transpose of eulerrotmat.m:81, sequence
+    123, moving axes); derotmat3d(rotmat3d(ang)) returns ang."""
+    so, co, sp, cp, sk, ck = (f(float(a)) for a in ang for f in (np.sin, np.cos))
+    return np.array([[cp * ck, co * sk + so * sp * ck, so * sk - co * sp * ck],
+                     [-cp * sk, co * ck - so * sp * sk, so * ck + co * sp * sk],
+                     [sp, -so * cp, co * cp]])
 
 def resect(s0, cams='all', cpId=None, n=1, v=0.0, chkId=None, device=0):
     """Spatial resection of the listed camera stations from the control points with ids cpId; returns

@@ -398,6 +398,43 @@ int  dbat_hip_forwintersect(dbat_hip_handle *h, const double *x, const uint8_t *
 int  dbat_hip_resect(int32_t device, int32_t n_images, const int64_t *pt_start, const double *X, const double *xn,
                      const int64_t *tri_start, const int32_t *tri, double *P, double *rms);
 
+/* ---- network transforms (additive to ABI 5; csrc/align.hpp) -------------- */
+
+/* [T,R,d,alpha] = rigidalign(X, Y, scale) (misc/rigidalign.m:27-61; Soderkvist and Wedin 1993) for 3-D points: the
+ * similarity (scale != 0) or rigid-body transformation that minimises sum |alpha R x_i + d - y_i|^2 over the used
+ * columns.  No handle: the arrays are what the caller has.
+ *   X, Y    [3*n] column-major 3 x n          use  [n], 0 drops the column whatever it holds; NULL: all are used
+ *   T       [16] out: [alpha R, d; 0 0 0 1], column-major (R = T(1:3,1:3) / alpha, d = T(1:3,4))
+ *   stats   [4]  out: alpha; the rms of the residuals, sqrt(sum |r_i|^2 / columns used); the columns used; the ratio
+ *                of the second to the first singular value of C
+ *   resid   [3*n] out, or NULL: alpha R x + d - y per used column, NaN for the others
+ * Three passes over the columns on the device: the count and the centroids xm, ym (rigidalign.m:36-37); the centred
+ * C = sum (y - ym)(x - xm)' (:40-43) with sum |x - xm|^2, which is tr(A'A) of :54 without its n x n matrix; and, once
+ * the host has R = P diag(1, 1, det(P Q')) Q' from the 3 x 3 SVD C = P S Q' (:46-49, Jacobi rotations, no LAPACK),
+ * alpha = tr((R A)'B) / tr(A'A) (:52-55) and d = ym - alpha R xm (:60), the residuals.  Every sum is a tree of fixed
+ * shape without floating-point atomics: two calls give the same bits.
+ * DBAT_HIP_EINVAL, before any device call (and so without a device): fewer than three used columns; a used column
+ * that is not finite; a second singular value of C at or below 1e-12 of the first -- collinear points do not define
+ * the rotation, rigidalign.m returns an arbitrary one.  Then DBAT_HIP_EDEVICE without a HIP device (no CPU path). */
+int  dbat_hip_rigidalign(int32_t device, int64_t n, const double *X, const double *Y, const uint8_t *use, int32_t scale,
+                         double *T, double *stats, double *resid);
+
+/* [EO,OP,fail] = pm_multixform(EO, OP, T) (photogrammetry/pm_multixform.m:11-40): the similarity T = [A d; 0 0 0 1],
+ * A = alpha R, applied to every object point (A x + d, :15-17) and every camera station (:20-39), in place.
+ *   T     [16] column-major               EO  [eo_rows*n_images], eo_rows >= 6: rows 0 .. 5 centre and omega, phi,
+ *   OP    [3*n_points]                        kappa in radians; further rows are not touched
+ *   fail  [n_images] out, or NULL: 1 for a camera whose six values are not all finite (:27-34); its column stays as
+ *         it is.  A point with a NaN coordinate becomes NaN in all three.
+ * The camera matrix M' [I, -c] inv(T) of :23-25 is (M' R' / alpha) [I, -(A c + d)]: the new centre is A c + d, the new
+ * world-to-camera rotation M' R', and omega, phi, kappa are those of derotmat3d.m:17-19 for that matrix.  (:37 takes
+ * them from M' R' / alpha with the scale still in it: phi = asin(M31 / alpha) is wrong for every alpha != 1.  Here the
+ * scale is divided out; for alpha = 1 the two agree.)  alpha = det(A)^(1/3).
+ * DBAT_HIP_EINVAL, before any device call: eo_rows < 6; a T that is not finite, whose last row is not [0 0 0 1], or
+ * whose A is not alpha times a proper rotation to 1e-9 in || A'A / alpha^2 - I ||_inf.  Then DBAT_HIP_EDEVICE without
+ * a HIP device.  n_images and n_points may be 0. */
+int  dbat_hip_multixform(int32_t device, const double *T, int64_t n_images, int32_t eo_rows, double *EO, int64_t n_points,
+                         double *OP, uint8_t *fail);
+
 /* ---- measurement hooks -------------------------------------------------- */
 
 /* One benchmark step = one Levenberg-Marquardt iteration's device work at
