@@ -88,12 +88,31 @@ struct DevBuf {
         n = count;
         if (count) HIPCHK(hipMalloc((void **)&p, count * sizeof(T)));
     }
-    template <class A>
-    void upload(const std::vector<T, A> &v) {
-        alloc(v.size());
-        if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    void upload(const T *src, size_t count) {
+        alloc(count);
+        if (count) HIPCHK(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
     }
+    template <class A>
+    void upload(const std::vector<T, A> &v) { upload(v.data(), v.size()); }
     ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// Device events around N consecutive spans of a stream's work: start() opens the first, every lap() closes one and opens
+// the next; read(), once the stream has been waited for, leaves their milliseconds in ms[] and returns the first.  The
+// first start() creates the events: a timer that was never started owns none, and its lap() and read() do nothing.
+static double event_ms(hipEvent_t a, hipEvent_t b) { float t = 0; HIPCHK(hipEventElapsedTime(&t, a, b)); return t; }
+template <int N>
+struct EventTimer {
+    hipEvent_t ev[N + 1] = {};
+    int n = 0;
+    double ms[N] = {};
+    ~EventTimer() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+    void start(hipStream_t s) {
+        if (!ev[0]) for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipEventRecord(ev[n = 0], s));
+    }
+    void lap(hipStream_t s) { if (ev[0]) HIPCHK(hipEventRecord(ev[++n], s)); }
+    double read() { for (int i = 0; ev[0] && i < N; ++i) ms[i] = event_ms(ev[i], ev[i + 1]); return ms[0]; }
 };
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -556,11 +575,7 @@ struct Core {
         st_on = false;
         HIPCHK(hipStreamSynchronize(stream));
         for (int i = 0; i < 5; ++i) out5[i] = 0.0;
-        for (size_t i = 0; i + 1 < st_id.size(); ++i) {
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, st_ev[i], st_ev[i + 1]));
-            out5[st_id[i]] += 1e-3 * ms;
-        }
+        for (size_t i = 0; i + 1 < st_id.size(); ++i) out5[st_id[i]] += 1e-3 * event_ms(st_ev[i], st_ev[i + 1]);
     }
     // sum of [S | g_red | g_c | diagU | scalars] over the ranks: the envelope of S is packed
     // next to the vectors, one all-reduce, unpacked again
@@ -1236,122 +1251,6 @@ struct Core {
         HIPCHK(hipMemcpyAsync(hqvv, qvv.p, (size_t)3 * P.no * sizeof(double), hipMemcpyDeviceToHost, stream));
         sync();
     }
-    // ---- ray intersection angles at zt (angles.hpp).  What the kernels need beyond the plan's uploads -- where every
-    // point's observations start, where every image's observations are in the camera-major copy, the work items of the
-    // pair kernel, the scratch array of unit directions -- is built by the first call and kept; a handle that never
-    // asks for angles has none of it.  The point side follows the plan's classification: the tiled points (at most
-    // CMAX rays) take the lane-group kernel, everything after the tiled batches (heavy and giant points; every point
-    // where nothing is tiled) a workgroup each.
-    struct AnglePlan {
-        bool ready = false;
-        int32_t hp0 = 0, hp1 = 0;                        // heavy / giant points: [hp0, hp1) of the processing order
-        int32_t heavy_kmax = 0;
-        int64_t n_items = 0, n_slots = 0, n_mfma = 0;
-        std::vector<int32_t> op_rays, cam_rays;          // per point (caller's order), per image
-        DevBuf<int64_t> pt_pos, cam_src, cam_pad;
-        DevBuf<int32_t> items;
-        DevBuf<double> cdir, op_out, cam_out;
-        DevBuf<unsigned long long> cam_min;
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-        double ms[3] = {0, 0, 0};                        // last call: point kernels, directions of the images, pair kernel + finish
-        ~AnglePlan() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
-    } ang;
-    void angle_plan() {
-        if (ang.ready) return;
-        const int64_t npt = P.np, no = nobs;
-        std::vector<int64_t> pos((size_t)npt + 1, 0);
-        for (int64_t o = 0; o < no; ++o) ++pos[(size_t)P.o_pt[o] + 1];
-        ang.op_rays.assign((size_t)npt, 0);
-        for (int64_t r = 0; r < npt; ++r) ang.op_rays[P.porder[r]] = (int32_t)pos[r + 1];
-        for (int64_t r = 0; r < npt; ++r) pos[r + 1] += pos[r];
-        const int64_t ho0 = P.batch_start[std::min<int64_t>(P.nb_tiled, nb)];
-        ang.hp1 = no > 0 ? P.o_pt[no - 1] + 1 : 0;
-        ang.hp0 = ho0 < no ? P.o_pt[ho0] : ang.hp1;
-        ang.heavy_kmax = 0;
-        for (int64_t r = 0; r < ang.hp0; ++r)
-            if (pos[r + 1] - pos[r] > ANG_LIGHT_KMAX) throw DeviceError{"internal: a tiled point with more rays than the angle kernel holds"};
-        for (int64_t r = ang.hp0; r < ang.hp1; ++r) ang.heavy_kmax = (int32_t)std::max<int64_t>(ang.heavy_kmax, pos[r + 1] - pos[r]);
-        if (ang.heavy_kmax > ANG_HEAVY_KMAX)
-            throw UsageError{"ray angles: an object point with " + std::to_string(ang.heavy_kmax) + " rays (at most " + std::to_string(ANG_HEAVY_KMAX) + ")"};
-        // images: their ranges in the two parts of the camera-major copy, 16-direction tiles, work items
-        std::vector<int64_t> src((size_t)4 * P.nc, 0), pad((size_t)P.nc + 1, 0);
-        for (int64_t q = 0; q < n_cm_chunks_all; ++q) {
-            const int c = P.cm_chunk_cam[q];
-            const int64_t len = P.cm_chunk_start[q + 1] - P.cm_chunk_start[q];
-            int64_t *sc = src.data() + 4 * (size_t)c;        // {first tiled, tiled, first of the rest, all}
-            if (q < n_cm_chunks) {
-                if (sc[1] == 0) sc[0] = P.cm_chunk_start[q];
-                sc[1] += len;
-            } else if (sc[3] == sc[1]) sc[2] = P.cm_chunk_start[q];   // (the chunks of the tiled part all come first)
-            sc[3] += len;
-        }
-        ang.cam_rays.assign((size_t)P.nc, 0);
-        std::vector<int32_t> items;
-        ang.n_mfma = 0;
-        for (int c = 0; c < P.nc; ++c) {
-            const int64_t n = src[4 * (size_t)c + 3];
-            if (n >= ((int64_t)1 << 31) - 16) throw UsageError{"ray angles: an image with more than 2^31 points"};
-            ang.cam_rays[c] = (int32_t)n;
-            const int64_t T = (n + 15) / 16;
-            pad[(size_t)c + 1] = pad[c] + 16 * T;
-            if (n >= 2) {
-                for (int64_t I0 = 0; I0 < T; I0 += ANG_RUN) { items.push_back(c); items.push_back((int32_t)I0); }
-                ang.n_mfma += T * (T + 1) / 2;
-            }
-        }
-        ang.n_items = (int64_t)items.size() / 2;
-        ang.n_slots = pad[P.nc];
-        ang.pt_pos.upload(pos); ang.cam_src.upload(src); ang.cam_pad.upload(pad); ang.items.upload(items);
-        ang.cdir.alloc((size_t)3 * std::max<int64_t>(ang.n_slots, 1));
-        ang.op_out.alloc((size_t)std::max<int64_t>(npt, 1)); ang.cam_out.alloc((size_t)std::max(P.nc, 1));
-        ang.cam_min.alloc((size_t)std::max(P.nc, 1));
-        for (auto &e : ang.ev) HIPCHK(hipEventCreate(&e));
-        ang.ready = true;
-    }
-    void ray_angles(double *hop, double *hcam, int32_t *hop_rays, int32_t *hcam_rays) {
-        angle_plan();
-        if (hop_rays) std::copy(ang.op_rays.begin(), ang.op_rays.end(), hop_rays);
-        if (hcam_rays) std::copy(ang.cam_rays.begin(), ang.cam_rays.end(), hcam_rays);
-        if (!hop && !hcam) return;
-        prep_cams(zt.p);
-        const double *zz = zt.p;
-        HIPCHK(hipEventRecord(ang.ev[0], stream));
-        if (hop) {
-            if (ang.hp0 > 0)
-                launch<k_angles_pt_light>(dim3((unsigned)cdiv(ang.hp0, ANG_LIGHT_PTS)), dim3(256), 0, zz, (int64_t)P.NS, cams.p, o_cam.p, ang.pt_pos.p, ang.hp0, ang.op_out.p);
-            if (ang.hp1 > ang.hp0)
-                launch<k_angles_pt_heavy>(dim3((unsigned)(ang.hp1 - ang.hp0)), dim3(256), (size_t)3 * ang.heavy_kmax * sizeof(double), zz, (int64_t)P.NS, cams.p,
-                                          o_cam.p, ang.pt_pos.p, ang.hp0, ang.heavy_kmax, ang.op_out.p);
-        }
-        HIPCHK(hipEventRecord(ang.ev[1], stream));
-        if (hcam) {
-            HIPCHK(hipMemsetAsync(ang.cam_min.p, 0xFF, (size_t)P.nc * sizeof(unsigned long long), stream));
-            if (ang.n_slots > 0)
-                launch<k_angles_cam_dirs>(dim3((unsigned)cdiv(ang.n_slots, 256)), dim3(256), 0, zz, (int64_t)P.NS, cams.p, P.nc, cm_pt.p, ang.cam_src.p, ang.cam_pad.p, ang.cdir.p);
-        }
-        HIPCHK(hipEventRecord(ang.ev[2], stream));
-        if (hcam) {
-            if (ang.n_items > 0)
-                launch<k_angles_cam_pairs>(dim3((unsigned)ang.n_items), dim3(256), 0, ang.cdir.p, ang.cam_pad.p, ang.items.p, ang.cam_min.p);
-            launch<k_angles_cam_finish>(dim3((unsigned)cdiv(P.nc, 256)), dim3(256), 0, P.nc, ang.cam_src.p, ang.cam_min.p, ang.cam_out.p);
-        }
-        HIPCHK(hipEventRecord(ang.ev[3], stream));
-        std::vector<double> tmp;
-        if (hop && ang.hp1 > 0) {
-            tmp.resize((size_t)ang.hp1);
-            HIPCHK(hipMemcpyAsync(tmp.data(), ang.op_out.p, (size_t)ang.hp1 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        }
-        if (hcam) HIPCHK(hipMemcpyAsync(hcam, ang.cam_out.p, (size_t)P.nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-        sync();
-        if (hop) {                                       // device values are in processing order; the unobserved points come last
-            for (int64_t r = 0; r < P.np; ++r) hop[P.porder[r]] = r < ang.hp1 ? tmp[r] : std::nan("");
-        }
-        for (int i = 0; i < 3; ++i) {
-            float t = 0;
-            HIPCHK(hipEventElapsedTime(&t, ang.ev[i], ang.ev[i + 1]));
-            ang.ms[i] = t;
-        }
-    }
     // camera-major slot of every owned observation (processing order): the plan's stable counting sort by camera, tiled
     // part first
     std::vector<int32_t> cm_slots() const {
@@ -1367,10 +1266,8 @@ struct Core {
         }
         return cmm;
     }
-    // ---- point depths and the chirality veto at zt (depth.hpp).  What the kernels need beyond the plan's uploads -- the
-    // IP column of every slot of the camera-major copy, the scratch of the reductions, the depths in IP-column order --
-    // is built by the first call (or by set_chirality) and kept: no allocation per call, none inside a damping loop.
-    // The camera records are cams_f, the ones eval_f / eval_f_step leave at the point they evaluated.
+    // ---- point depths and the chirality veto (depth.hpp): the state that depth_host.hpp builds and uses.  It lives
+    // here because the damping loops consult the veto (vetoed()).
     struct DepthPlan {
         bool ready = false;
         DevBuf<int64_t> cm_col;
@@ -1378,55 +1275,9 @@ struct Core {
         DevBuf<unsigned long long> red;                  // [0] count, [1] smallest key, [2, 2 + nc) per image, then per chunk
         DevBuf<double> depth;
         std::vector<unsigned long long> img_host;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        double ms = 0;                                   // last point_depths: reset of the scratch + the two kernels
-        ~DepthPlan() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+        EventTimer<1> timer;                             // last point_depths: reset of the scratch + the two kernels
     } dep;
     static constexpr int DEPTH_SLOT = 52;                // mailbox slots 52..54: no other kernel writes them
-    void depth_plan() {
-        if (dep.ready) return;
-        std::vector<int64_t> col((size_t)std::max<int64_t>(nobs, 1), 0);
-        const std::vector<int32_t> cmm = cm_slots();
-        for (int64_t o = 0; o < nobs; ++o) col[(size_t)cmm[o]] = P.o_row[o];
-        dep.cm_col.upload(col);
-        dep.chunk_col.alloc((size_t)std::max<int64_t>(n_cm_chunks_all, 1));
-        dep.red.alloc((size_t)(2 + std::max(P.nc, 1) + std::max<int64_t>(n_cm_chunks_all, 1)));
-        dep.depth.alloc((size_t)std::max<int64_t>(P.no, 1));
-        dep.img_host.resize((size_t)std::max(P.nc, 1));
-        for (auto &e : dep.ev) HIPCHK(hipEventCreate(&e));
-        dep.ready = true;
-    }
-    // the depth kernels at zz with the camera records cams_f; FULL: depths, per-image minima and the argmin as well.
-    // Results: the mailbox (hpin[DEPTH_SLOT ..]) once the stream has run (ticket mb_seq).
-    template <bool FULL>
-    void depth_enqueue(const double *zz, double thr, bool want_depth) {
-        HIPCHK(hipMemsetAsync(dep.red.p, 0, sizeof(unsigned long long), stream));
-        HIPCHK(hipMemsetAsync(dep.red.p + 1, 0xFF, (size_t)(FULL ? 1 + P.nc : 1) * sizeof(unsigned long long), stream));
-        unsigned long long *img = dep.red.p + 2, *ckey = dep.red.p + 2 + std::max(P.nc, 1);
-        if (n_cm_chunks_all > 0)
-            launch<k_depth_cm<FULL>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, zz, (int64_t)P.NS, (const CamRec *)cams_f.p, (const int32_t *)cm_pt.p,
-                                     (const int32_t *)cm_chunk_cam.p, (const int64_t *)cm_chunk_start.p, (const int64_t *)dep.cm_col.p, thr,
-                                     want_depth ? dep.depth.p : (double *)nullptr, dep.red.p, img, ckey, dep.chunk_col.p);
-        launch<k_depth_finish<FULL>>(dim3(1), dim3(256), 0, n_cm_chunks_all, (const unsigned long long *)dep.red.p, (const unsigned long long *)ckey,
-                                     (const long long *)dep.chunk_col.p, hpin, DEPTH_SLOT, ++mb_seq);
-    }
-    static int64_t mailbox_int(const double *slot) { int64_t v; memcpy(&v, slot, sizeof v); return v; }
-    void point_depths(double thr, double *hdepth, double *himg, int64_t &n_behind, double &min_depth, int64_t &argmin) {
-        depth_plan();
-        prep_cams(zt.p, cams_f.p);
-        HIPCHK(hipEventRecord(dep.ev[0], stream));
-        depth_enqueue<true>(zt.p, thr, hdepth != nullptr);
-        HIPCHK(hipEventRecord(dep.ev[1], stream));
-        if (hdepth && P.no > 0) HIPCHK(hipMemcpyAsync(hdepth, dep.depth.p, (size_t)P.no * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (himg && P.nc > 0)
-            HIPCHK(hipMemcpyAsync(dep.img_host.data(), dep.red.p + 2, (size_t)P.nc * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-        sync();                                          // (not armed: the copies behind the ticket are waited for too)
-        if (himg) for (int c = 0; c < P.nc; ++c) himg[c] = depth_from_key(dep.img_host[c]);
-        n_behind = mailbox_int(hpin + DEPTH_SLOT); min_depth = hpin[DEPTH_SLOT + 1]; argmin = mailbox_int(hpin + DEPTH_SLOT + 2);
-        float t = 0;
-        HIPCHK(hipEventElapsedTime(&t, dep.ev[0], dep.ev[1]));
-        dep.ms = t;
-    }
     // The built-in chirality veto (dbat_hip_set_chirality): at every trial point a damping loop consults its veto at,
     // the number of observations with !(depth > chir_thr) at zt; a non-zero count rejects.  Two words cross to the host
     // (the count and the smallest depth, kept for dbat_hip_chirality_stats), the parameter vector never does.
@@ -1434,151 +1285,8 @@ struct Core {
     double chir_thr = 0.0;
     int64_t veto_tested = 0, veto_rejected = 0, veto_n_behind = 0;
     double veto_min_depth = NAN;
-    void set_chirality(bool on, double thr) {
-        if (on) depth_plan();
-        chirality = on; chir_thr = thr;
-    }
     void veto_stats_reset() { veto_tested = veto_rejected = veto_n_behind = 0; veto_min_depth = NAN; }
-    bool chirality_veto() {                              // right after eval_f_step: cams_f are the trial point's records
-        stage(3);
-        depth_enqueue<false>(zt.p, chir_thr, false);
-        mb_armed = true;
-        sync();
-        const int64_t nb = mailbox_int(hpin + DEPTH_SLOT);
-        ++veto_tested;
-        if (nb == 0) return false;
-        ++veto_rejected; veto_n_behind = nb; veto_min_depth = hpin[DEPTH_SLOT + 1];
-        return true;
-    }
-    // ---- image coverage and marking-residual statistics (quality.hpp).  Built by the first call and kept, as the
-    // angles' plan: the columns of every image (IP is image-major), where every point's observations start, the
-    // measured pixel coordinates in IP order (the observations are structure: dbat_hip_set_values never changes them;
-    // the principal point is read from io_fixed, which it does change), the index scratch of the images with more
-    // than QUAL_HULL_CAP points.
-    struct QualPlan {
-        bool ready = false;
-        int32_t hp0 = 0, hp1 = 0;                        // heavy / giant points: [hp0, hp1) of the processing order
-        std::vector<int64_t> ip_start;                   // [nc + 1]
-        std::vector<int64_t> op_n;                       // per point (caller's order)
-        DevBuf<int64_t> d_ip_start, pt_pos, big_off, rad_ip, hull_start, hull_ip, cam_max_ip, max_ip;
-        DevBuf<int32_t> big_idx, hull_tmp, hull_n;
-        DevBuf<double> ip_uv, lo, hi, rad_max, hull_area, r, e2, cam_ss, cam_max, op_ss, tot;
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-        double ms[2] = {0, 0};                           // last dbat_hip_coverage, last dbat_hip_residual_stats (kernels only)
-        ~QualPlan() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
-    } qual;
-    void qual_plan() {
-        if (qual.ready) return;
-        const int64_t npt = P.np, no = nobs;
-        const int nc = P.nc;
-        qual.ip_start.assign((size_t)nc + 1, 0);
-        for (int64_t o = 0; o < no; ++o) ++qual.ip_start[(size_t)P.o_cam[o] + 1];
-        for (int c = 0; c < nc; ++c) qual.ip_start[(size_t)c + 1] += qual.ip_start[c];
-        std::vector<int64_t> pos((size_t)npt + 1, 0);
-        for (int64_t o = 0; o < no; ++o) {
-            const int c = P.o_cam[o];
-            if (P.o_row[o] < qual.ip_start[c] || P.o_row[o] >= qual.ip_start[(size_t)c + 1])
-                throw UsageError{"network quality: the image points are not image-major (the columns of an image must be contiguous, images ascending)"};
-            ++pos[(size_t)P.o_pt[o] + 1];
-        }
-        qual.op_n.assign((size_t)npt, 0);
-        for (int64_t r = 0; r < npt; ++r) qual.op_n[P.porder[r]] = pos[r + 1];
-        for (int64_t r = 0; r < npt; ++r) pos[r + 1] += pos[r];
-        const int64_t ho0 = P.batch_start[std::min<int64_t>(P.nb_tiled, nb)];
-        qual.hp1 = no > 0 ? P.o_pt[no - 1] + 1 : 0;
-        qual.hp0 = ho0 < no ? P.o_pt[ho0] : qual.hp1;
-        std::vector<int64_t> boff((size_t)nc, 0);
-        int64_t nbig = 0;
-        for (int c = 0; c < nc; ++c) {
-            const int64_t n = qual.ip_start[(size_t)c + 1] - qual.ip_start[c];
-            if (n >= ((int64_t)1 << 30)) throw UsageError{"network quality: an image with more than 2^30 points"};
-            boff[c] = nbig;
-            if (n > QUAL_HULL_CAP) { int64_t m2 = 1; while (m2 < n) m2 <<= 1; nbig += m2; }
-        }
-        qual.d_ip_start.upload(qual.ip_start); qual.pt_pos.upload(pos); qual.big_off.upload(boff);
-        qual.big_idx.alloc((size_t)std::max<int64_t>(nbig, 1));
-        const size_t nc1 = (size_t)std::max(nc, 1), no1 = (size_t)std::max<int64_t>(no, 1);
-        qual.ip_uv.alloc(2 * no1);
-        qual.hull_tmp.alloc(no1 + nc1); qual.hull_n.alloc(nc1); qual.hull_start.alloc(nc1 + 1); qual.hull_ip.alloc(no1);
-        qual.lo.alloc(2 * nc1); qual.hi.alloc(2 * nc1); qual.rad_max.alloc(nc1); qual.rad_ip.alloc(nc1); qual.hull_area.alloc(nc1);
-        qual.r.alloc(2 * no1); qual.e2.alloc(no1); qual.cam_ss.alloc(nc1); qual.cam_max.alloc(nc1); qual.cam_max_ip.alloc(nc1);
-        qual.op_ss.alloc((size_t)std::max<int64_t>(npt, 1)); qual.tot.alloc(2); qual.max_ip.alloc(1);
-        if (no > 0) launch<k_qual_ip_uv>(dim3((unsigned)cdiv(no, 256)), dim3(256), 0, no, o_row.p, o_uv.p, qual.ip_uv.p);
-        for (auto &e : qual.ev) HIPCHK(hipEventCreate(&e));
-        qual.ready = true;
-    }
-    static constexpr size_t qual_hull_lds = ((size_t)QUAL_HULL_CAP * 20 + ((size_t)QUAL_HULL_CAP + 1) * 4 + 7) / 8 * 8;
-    void coverage(double *hlo, double *hhi, double *hrad, int64_t *hrad_ip, double *harea, int64_t *hstart, int64_t *hip_) {
-        qual_plan();
-        const int nc = P.nc;
-        HIPCHK(hipEventRecord(qual.ev[0], stream));
-        if (nc > 0)
-            launch<k_qual_hull>(dim3((unsigned)nc), dim3(QUAL_THREADS), qual_hull_lds, qual.d_ip_start.p, qual.ip_uv.p, px.p, io_fixed.p, P.nIOrows,
-                                qual.big_idx.p, qual.big_off.p, qual.lo.p, qual.hi.p, qual.rad_max.p, qual.rad_ip.p, qual.hull_area.p,
-                                qual.hull_tmp.p, qual.hull_n.p);
-        HIPCHK(hipEventRecord(qual.ev[1], stream));
-        if (hlo) HIPCHK(hipMemcpyAsync(hlo, qual.lo.p, (size_t)2 * nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (hhi) HIPCHK(hipMemcpyAsync(hhi, qual.hi.p, (size_t)2 * nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (hrad) HIPCHK(hipMemcpyAsync(hrad, qual.rad_max.p, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (hrad_ip) HIPCHK(hipMemcpyAsync(hrad_ip, qual.rad_ip.p, (size_t)nc * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-        if (harea) HIPCHK(hipMemcpyAsync(harea, qual.hull_area.p, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-        std::vector<int32_t> hn((size_t)nc);
-        std::vector<int64_t> hs((size_t)nc + 1, 0);
-        if (hstart || hip_) HIPCHK(hipMemcpyAsync(hn.data(), qual.hull_n.p, (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        sync();
-        float t = 0;
-        HIPCHK(hipEventElapsedTime(&t, qual.ev[0], qual.ev[1]));
-        qual.ms[0] = t;
-        if (!hstart && !hip_) return;
-        for (int c = 0; c < nc; ++c) hs[(size_t)c + 1] = hs[c] + hn[c];
-        if (hstart) std::copy(hs.begin(), hs.end(), hstart);
-        if (!hip_ || hs[nc] == 0) return;
-        HIPCHK(hipMemcpyAsync(qual.hull_start.p, hs.data(), ((size_t)nc + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-        launch<k_qual_hull_pack>(dim3((unsigned)nc), dim3(256), 0, qual.d_ip_start.p, qual.hull_tmp.p, qual.hull_start.p, qual.hull_ip.p);
-        HIPCHK(hipMemcpyAsync(hip_, qual.hull_ip.p, (size_t)hs[nc] * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-        sync();
-    }
-    // at zt
-    void residual_stats(int64_t *hcam_n, double *hcam_ss, int64_t *hop_n, double *hop_ss, double *htot, double *hmax, int64_t *hmax_ip) {
-        qual_plan();
-        const int nc = P.nc;
-        if (hcam_n) for (int c = 0; c < nc; ++c) hcam_n[c] = qual.ip_start[(size_t)c + 1] - qual.ip_start[c];
-        if (hop_n) std::copy(qual.op_n.begin(), qual.op_n.end(), hop_n);
-        if (!hcam_ss && !hop_ss && !htot && !hmax && !hmax_ip) return;
-        const double *zz = zt.p;
-        prep_cams(zz, cams_f.p);
-        HIPCHK(hipEventRecord(qual.ev[0], stream));
-        if (nobs > 0)
-            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(uv_pre, [&](auto PRE) {
-                launch<k_residual<M, PRE>>(dim3(grid_obs), dim3(256), 0, d, zz, cams_f.p, rpart.p, (double *)nullptr, qual.r.p);
-            }); });
-        if (nc > 0)
-            launch<k_qual_cam_res>(dim3((unsigned)nc), dim3(256), 0, qual.d_ip_start.p, qual.r.p, px.p, qual.e2.p, qual.cam_ss.p, qual.cam_max.p, qual.cam_max_ip.p);
-        if (hop_ss) {
-            if (qual.hp0 > 0) launch<k_qual_pt_light>(dim3((unsigned)cdiv(qual.hp0, 256)), dim3(256), 0, qual.pt_pos.p, o_row.p, qual.e2.p, qual.hp0, qual.op_ss.p);
-            if (qual.hp1 > qual.hp0) launch<k_qual_pt_heavy>(dim3((unsigned)(qual.hp1 - qual.hp0)), dim3(64), 0, qual.pt_pos.p, o_row.p, qual.e2.p, qual.hp0, qual.op_ss.p);
-        }
-        launch<k_qual_total>(dim3(1), dim3(256), 0, nc, qual.cam_ss.p, qual.cam_max.p, qual.cam_max_ip.p, qual.tot.p, qual.max_ip.p);
-        HIPCHK(hipEventRecord(qual.ev[1], stream));
-        std::vector<double> tmp;
-        double tot[2] = {0, 0};
-        int64_t mip = -1;
-        if (hcam_ss) HIPCHK(hipMemcpyAsync(hcam_ss, qual.cam_ss.p, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (hop_ss && qual.hp1 > 0) {
-            tmp.resize((size_t)qual.hp1);
-            HIPCHK(hipMemcpyAsync(tmp.data(), qual.op_ss.p, (size_t)qual.hp1 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        }
-        HIPCHK(hipMemcpyAsync(tot, qual.tot.p, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(&mip, qual.max_ip.p, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-        sync();
-        if (hop_ss) for (int64_t r = 0; r < P.np; ++r) hop_ss[P.porder[r]] = r < qual.hp1 ? tmp[r] : 0.0;   // (the unobserved points come last)
-        if (htot) *htot = tot[0];
-        if (hmax) *hmax = tot[1];
-        if (hmax_ip) *hmax_ip = mip;
-        float t = 0;
-        HIPCHK(hipEventElapsedTime(&t, qual.ev[0], qual.ev[1]));
-        qual.ms[1] = t;
-    }
+    bool chirality_veto();                               // right after eval_f_step (depth_host.hpp)
     // ---- robust reweighting (robust.hpp).  A handle that never sees a robust call has none of this: pw follows the
     // plan (uniform weights: the camera records' weights, no o_w / sg_w / cm_w).  robust_promote() gives every owned
     // observation its own weights (o_w = o_w_base * sqrt(omega)) and keeps the maps from processing order to the
@@ -2037,33 +1745,7 @@ static void loop_lmp(Core &c, const dbat_hip_options &o, double delta0, LoopOut 
     c.settle_lin_point();
 }
 
-}  // namespace dbat
-
-// ---- network transforms (align.hpp): helpers of dbat_hip_rigidalign / dbat_hip_multixform ----
-namespace dbat {
-
-// device events around the kernels of the last call on this thread: [0] centroids [1] cross products [2] residuals
-// (dbat_hip_rigidalign), [3] points [4] cameras (dbat_hip_multixform), each pass with its finishing launch; 0: not launched
-static thread_local double g_align_ms[5] = {0, 0, 0, 0, 0};
-static thread_local bool g_align_timing = false;         // dbat_hip_debug_align_timing: off, no event is created
-
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    explicit EventPair(bool on) { if (on) { HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b)); } }
-    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    void start() { if (a) HIPCHK(hipEventRecord(a, (hipStream_t)nullptr)); }
-    void stop() { if (b) HIPCHK(hipEventRecord(b, (hipStream_t)nullptr)); }
-    double ms() { float t = 0; if (b) { HIPCHK(hipEventSynchronize(b)); HIPCHK(hipEventElapsedTime(&t, a, b)); } return t; }
-};
-
-template <class T>
-static void upload_raw(DevBuf<T> &b, const T *src, size_t count) {
-    b.alloc(count);
-    if (count) HIPCHK(hipMemcpy(b.p, src, count * sizeof(T), hipMemcpyHostToDevice));
-}
-
-static const char *const ALIGN_COLLINEAR = "rigidalign: the used points are collinear or coincide (second singular value of the "
-                                           "cross-product matrix <= 1e-12 of the first): the rotation is not defined";
+struct PointIndex; struct AnglePlan; struct QualPlan;         // analysis_host.hpp, angles_host.hpp, quality_host.hpp
 
 }  // namespace dbat
 
@@ -2074,6 +1756,11 @@ using namespace dbat;
 
 struct dbat_hip_handle {
     std::unique_ptr<Core> core;
+    // what the network analyses build on their first call and keep; the engine never sees it
+    std::unique_ptr<PointIndex> pts;
+    std::unique_ptr<AnglePlan> ang;
+    std::unique_ptr<QualPlan> qual;
+    __attribute__((visibility("hidden"))) ~dbat_hip_handle() = default;     // (no symbol of the ABI)
 };
 
 #define API_TRY try {
@@ -2083,6 +1770,12 @@ struct dbat_hip_handle {
     catch (const UsageError &e) { g_err = e.msg; return DBAT_HIP_EINVAL; }              \
     catch (const std::bad_alloc &) { g_err = "out of host memory"; return DBAT_HIP_ENOMEM; } \
     catch (const std::exception &e) { g_err = e.what(); return DBAT_HIP_EINVAL; }
+
+// ---- the network analyses: plan, drivers and C entry points of each beside its kernels (the transforms: at the end) ----
+#include "analysis_host.hpp"
+#include "angles_host.hpp"
+#include "depth_host.hpp"
+#include "quality_host.hpp"
 
 extern "C" {
 
@@ -2890,27 +2583,17 @@ int dbat_hip_bench_step(dbat_hip_handle *h, double lambda, int32_t scale_columns
     c.timing = false;
     c.have_lin = true; c.lambda_lin = lambda; c.scale_lin = scale_columns; c.s_valid = false;
     if (ms) {
-        for (int i = 0; i < 4; ++i) {
-            float t = 0;
-            HIPCHK(hipEventElapsedTime(&t, c.ev[i], c.ev[i + 1]));
-            ms[i] = t;
-        }
-        for (int i = 0; i < 4; ++i) {      // k_build, potrf+potrs, k_backsub, k_residual
-            float t = 0;
-            HIPCHK(hipEventElapsedTime(&t, c.kev[2 * i], c.kev[2 * i + 1]));
-            ms[4 + i] = t;
-        }
+        for (int i = 0; i < 4; ++i) ms[i] = event_ms(c.ev[i], c.ev[i + 1]);
+        for (int i = 0; i < 4; ++i) ms[4 + i] = event_ms(c.kev[2 * i], c.kev[2 * i + 1]);      // k_build, potrf+potrs, k_backsub, k_residual
         for (int i = 8; i < 16; ++i) ms[i] = 0.0;
         if (c.use_heavy) {                                   // heavy / giant points: camera side + Z rows, then the products
-            float t = 0;
-            HIPCHK(hipEventElapsedTime(&t, c.kev[10], c.kev[11])); ms[12] = t;
-            HIPCHK(hipEventElapsedTime(&t, c.kev[11], c.kev[12])); ms[13] = t;
+            ms[12] = event_ms(c.kev[10], c.kev[11]);
+            ms[13] = event_ms(c.kev[11], c.kev[12]);
         }
         if (c.mg_subtree && c.multi() && c.use_perm) {      // domain sharding: the three parts of the factorisation
-            float t = 0;
-            HIPCHK(hipEventElapsedTime(&t, c.kev[2], c.kev[8])); ms[8] = t;       // own domain + shares of the top tiles
-            HIPCHK(hipEventElapsedTime(&t, c.kev[8], c.kev[9])); ms[9] = t;       // all-reduce of the top tiles
-            HIPCHK(hipEventElapsedTime(&t, c.kev[9], c.kev[3])); ms[10] = t;      // top separators + backward substitution
+            ms[8] = event_ms(c.kev[2], c.kev[8]);        // own domain + shares of the top tiles
+            ms[9] = event_ms(c.kev[8], c.kev[9]);        // all-reduce of the top tiles
+            ms[10] = event_ms(c.kev[9], c.kev[3]);       // top separators + backward substitution
         }
     }
     return DBAT_HIP_OK;
@@ -2936,268 +2619,6 @@ int dbat_hip_redundancy(dbat_hip_handle *h, const double *x, double *qvv_ip, dou
     DeviceGuard dev_guard(c.device);
     c.x_to_z(x, c.z.p);
     c.redundancy(qvv_ip, r_prior);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_ray_angles(dbat_hip_handle *h, const double *x, double *op_angle, double *cam_angle, int32_t *op_rays,
-                        int32_t *cam_rays) {
-    API_TRY
-    if (!h || !x) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    if (c.P.nranks > 1) {
-        g_err = "ray angles: this handle is one shard of " + std::to_string(c.P.nranks) +
-                " (the pairs of rays across shards are not formed; use a handle of the whole problem)";
-        return DBAT_HIP_EINVAL;
-    }
-    DeviceGuard dev_guard(c.device);
-    if (op_angle || cam_angle) c.x_to_z(x, c.zt.p);
-    c.ray_angles(op_angle, cam_angle, op_rays, cam_rays);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-static bool depth_one_rank(const Core &c, const char *what) {
-    if (c.P.nranks <= 1) return true;
-    g_err = std::string(what) + ": this handle is one shard of " + std::to_string(c.P.nranks) +
-            " (the counts and minima of the shards are not combined; use a handle of the whole problem)";
-    return false;
-}
-
-int dbat_hip_point_depths(dbat_hip_handle *h, const double *x, double thr, double *depth_out, double *img_min_out,
-                          dbat_hip_depth_stats *stats_out) {
-    API_TRY
-    if (!h || !x || !stats_out) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    if (thr != thr) { g_err = "point depths: the threshold is NaN"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    if (!depth_one_rank(c, "point depths")) return DBAT_HIP_EUNSUPPORTED;
-    DeviceGuard dev_guard(c.device);
-    c.x_to_z(x, c.zt.p);
-    c.point_depths(thr, depth_out, img_min_out, stats_out->n_behind, stats_out->min_depth, stats_out->argmin_column);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_set_chirality(dbat_hip_handle *h, int32_t on, double min_depth) {
-    API_TRY
-    if (!h) { g_err = "null handle"; return DBAT_HIP_EINVAL; }
-    if (!std::isfinite(min_depth)) { g_err = "chirality veto: min_depth must be finite"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    if (on && !depth_one_rank(c, "chirality veto")) return DBAT_HIP_EUNSUPPORTED;
-    DeviceGuard dev_guard(c.device);
-    c.set_chirality(on != 0, min_depth);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_chirality_stats(const dbat_hip_handle *h, dbat_hip_veto_stats *out) {
-    if (!h || !out) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    const Core &c = *h->core;
-    out->tested = c.veto_tested; out->rejected = c.veto_rejected; out->n_behind = c.veto_n_behind; out->min_depth = c.veto_min_depth;
-    return DBAT_HIP_OK;
-}
-
-/* Debug / measurement: the veto's own pass (the reset of its two words, k_depth_cm<false>, k_depth_finish<false>) at x,
- * reps times back to back between two device events: ms[0] = milliseconds per pass, ms[1] = the count it found. */
-int dbat_hip_debug_chirality_pass_ms(dbat_hip_handle *h, const double *x, int32_t reps, double *ms) {
-    API_TRY
-    if (!h || !x || !ms || reps < 1) { g_err = "bad argument"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    if (!depth_one_rank(c, "chirality veto")) return DBAT_HIP_EUNSUPPORTED;
-    DeviceGuard dev_guard(c.device);
-    c.depth_plan();
-    c.x_to_z(x, c.zt.p);
-    c.prep_cams(c.zt.p, c.cams_f.p);
-    HIPCHK(hipEventRecord(c.dep.ev[0], c.stream));
-    for (int i = 0; i < reps; ++i) c.depth_enqueue<false>(c.zt.p, c.chir_thr, false);
-    HIPCHK(hipEventRecord(c.dep.ev[1], c.stream));
-    c.sync();
-    float t = 0;
-    HIPCHK(hipEventElapsedTime(&t, c.dep.ev[0], c.dep.ev[1]));
-    ms[0] = t / reps; ms[1] = (double)Core::mailbox_int(c.hpin + Core::DEPTH_SLOT);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-/* Debug / measurement: milliseconds of the kernels of the last dbat_hip_point_depths on the handle's stream (device
- * events: the reset of the scratch, k_depth_cm, k_depth_finish). */
-int dbat_hip_debug_point_depths_ms(dbat_hip_handle *h, double *ms) {
-    if (!h || !ms || !h->core->dep.ready) { g_err = "no point depths computed on this handle"; return DBAT_HIP_EINVAL; }
-    ms[0] = h->core->dep.ms;
-    return DBAT_HIP_OK;
-}
-
-/* Debug / measurement: milliseconds of the last dbat_hip_ray_angles on the handle's stream (device events): ms[0] the
- * point kernels, ms[1] the unit directions of the images, ms[2] the pair kernel and the final acos; info[0] the
- * v_mfma_f64_16x16x4_f64 instructions (256 pairs each) of one launch of the pair kernel, info[1] its workgroups. */
-int dbat_hip_debug_ray_angles_ms(dbat_hip_handle *h, double *ms, int64_t *info) {
-    if (!h || !ms || !info || !h->core->ang.ready) { g_err = "no ray angles computed on this handle"; return DBAT_HIP_EINVAL; }
-    for (int i = 0; i < 3; ++i) ms[i] = h->core->ang.ms[i];
-    info[0] = h->core->ang.n_mfma; info[1] = h->core->ang.n_items;
-    return DBAT_HIP_OK;
-}
-
-/* Host only, one thread: the definition of dbat_hip_ray_angles over the problem's own arrays (angles.m:26-46,
- * camangles.m:26-46) with the arithmetic of the kernels (unit_dir, abs_dot, angle_from_min).  For tests of the
- * definition on a machine without a GPU; never on the product path. */
-int dbat_hip_debug_ray_angles_host(const dbat_hip_problem *prob, double *op_angle, double *cam_angle) {
-    API_TRY
-    if (!prob) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    if (prob->abi_version != DBAT_HIP_ABI_VERSION) { g_err = "ABI version mismatch"; return DBAT_HIP_EINVAL; }
-    const int64_t nc = prob->n_images, np = prob->n_points, no = prob->n_obs;
-    if (nc < 0 || np < 0 || no < 0 || (no > 0 && (!prob->ip_cam || !prob->ip_pt)) || (nc > 0 && !prob->EO_val) || (np > 0 && !prob->OP_val)) {
-        g_err = "bad problem"; return DBAT_HIP_EINVAL;
-    }
-    for (int64_t o = 0; o < no; ++o)
-        if (prob->ip_cam[o] < 0 || prob->ip_cam[o] >= nc || prob->ip_pt[o] < 0 || prob->ip_pt[o] >= np) { g_err = "IP index out of range"; return DBAT_HIP_EINVAL; }
-    // side 0: the rays of every point (apex = the point, ends = camera centres); side 1: of every image
-    for (int side = 0; side < 2; ++side) {
-        double *out = side == 0 ? op_angle : cam_angle;
-        if (!out) continue;
-        const int64_t n = side == 0 ? np : nc;
-        const int32_t *own = side == 0 ? prob->ip_pt : prob->ip_cam, *other = side == 0 ? prob->ip_cam : prob->ip_pt;
-        std::vector<int64_t> start((size_t)n + 1, 0);
-        for (int64_t o = 0; o < no; ++o) ++start[(size_t)own[o] + 1];
-        for (int64_t i = 0; i < n; ++i) start[i + 1] += start[i];
-        std::vector<int32_t> lst((size_t)no);
-        {
-            std::vector<int64_t> fill(start.begin(), start.end() - 1);
-            for (int64_t o = 0; o < no; ++o) lst[(size_t)fill[own[o]]++] = other[o];
-        }
-        std::vector<double> dir;
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t k = start[i + 1] - start[i];
-            dir.resize((size_t)3 * k);
-            for (int64_t j = 0; j < k; ++j) {
-                const int32_t e = lst[(size_t)(start[i] + j)];
-                const double *q = side == 0 ? prob->OP_val + 3 * i : prob->OP_val + 3 * (int64_t)e;
-                const double *cc = side == 0 ? prob->EO_val + 6 * (int64_t)e : prob->EO_val + 6 * i;
-                unit_dir(q, cc, dir[3 * j], dir[3 * j + 1], dir[3 * j + 2]);
-            }
-            double m = INFINITY;
-            for (int64_t a = 0; a < k; ++a)
-                for (int64_t b = a + 1; b < k; ++b)
-                    m = std::fmin(m, abs_dot(dir[3 * a], dir[3 * a + 1], dir[3 * a + 2], dir[3 * b], dir[3 * b + 1], dir[3 * b + 2]));
-            out[i] = angle_from_min(k, m);
-        }
-    }
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-static bool quality_one_rank(const Core &c, const char *what) {
-    if (c.P.nranks <= 1) return true;
-    g_err = std::string(what) + ": this handle is one shard of " + std::to_string(c.P.nranks) +
-            " (an image's points are spread over the shards; use a handle of the whole problem)";
-    return false;
-}
-
-int dbat_hip_coverage(dbat_hip_handle *h, double *lo, double *hi, double *rad_max, int64_t *rad_ip, double *hull_area,
-                      int64_t *hull_start, int64_t *hull_ip) {
-    API_TRY
-    if (!h) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    if (!quality_one_rank(c, "coverage")) return DBAT_HIP_EINVAL;
-    DeviceGuard dev_guard(c.device);
-    c.coverage(lo, hi, rad_max, rad_ip, hull_area, hull_start, hull_ip);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_residual_stats(dbat_hip_handle *h, const double *x, int64_t *cam_n, double *cam_ss, int64_t *op_n, double *op_ss,
-                            double *total_ss, double *max_e, int64_t *max_ip) {
-    API_TRY
-    if (!h || !x) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    if (!quality_one_rank(c, "residual statistics")) return DBAT_HIP_EINVAL;
-    DeviceGuard dev_guard(c.device);
-    if (cam_ss || op_ss || total_ss || max_e || max_ip) c.x_to_z(x, c.zt.p);
-    c.residual_stats(cam_n, cam_ss, op_n, op_ss, total_ss, max_e, max_ip);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int32_t dbat_hip_quality_hull_cap(void) { return QUAL_HULL_CAP; }
-
-/* Debug / measurement: milliseconds of the kernels of the last dbat_hip_coverage (ms[0]) and of the last
- * dbat_hip_residual_stats (ms[1], the residual pass included) on the handle's stream (device events). */
-int dbat_hip_debug_quality_ms(dbat_hip_handle *h, double *ms) {
-    if (!h || !ms || !h->core->qual.ready) { g_err = "no coverage or residual statistics computed on this handle"; return DBAT_HIP_EINVAL; }
-    ms[0] = h->core->qual.ms[0]; ms[1] = h->core->qual.ms[1];
-    return DBAT_HIP_OK;
-}
-
-/* Host only, one thread: dbat_hip_coverage over the problem's own arrays with the code of the kernel (octagon filter,
- * order, chain scan, shoelace sum of quality.hpp; std::sort in place of the network).  For tests on a machine without
- * a GPU; never on the product path. */
-int dbat_hip_debug_coverage_host(const dbat_hip_problem *prob, double *lo, double *hi, double *rad_max, int64_t *rad_ip,
-                                 double *hull_area, int64_t *hull_start, int64_t *hull_ip) {
-    API_TRY
-    if (!prob) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    if (prob->abi_version != DBAT_HIP_ABI_VERSION) { g_err = "ABI version mismatch"; return DBAT_HIP_EINVAL; }
-    const int64_t nc = prob->n_images, no = prob->n_obs;
-    if (nc < 0 || no < 0 || (no > 0 && (!prob->ip_cam || !prob->ip_val)) || (nc > 0 && (!prob->IO_val || !prob->px_size))) {
-        g_err = "bad problem"; return DBAT_HIP_EINVAL;
-    }
-    const int R = 5 + prob->nK + prob->nP;
-    std::vector<int64_t> start((size_t)nc + 1, 0);
-    for (int64_t o = 0; o < no; ++o) {
-        if (prob->ip_cam[o] < 0 || prob->ip_cam[o] >= nc || (o > 0 && prob->ip_cam[o] < prob->ip_cam[o - 1])) {
-            g_err = "IP.cam out of range or not image-major"; return DBAT_HIP_EINVAL;
-        }
-        ++start[(size_t)prob->ip_cam[o] + 1];
-    }
-    for (int64_t c = 0; c < nc; ++c) start[c + 1] += start[c];
-    const double nan = std::nan("");
-    std::vector<int32_t> idx, stk;
-    int64_t nh = 0;
-    if (hull_start) hull_start[0] = 0;
-    for (int64_t c = 0; c < nc; ++c) {
-        const int64_t i0 = start[c];
-        const int n = (int)(start[c + 1] - i0);
-        const double *uv = prob->ip_val + 2 * i0;
-        double l[2] = {nan, nan}, hh[2] = {nan, nan}, rm = nan, area = 0.0;
-        int64_t ri = -1;
-        int h = 0;
-        if (n > 0) {
-            double ev[9];
-            int ei[9];
-            for (int k = 0; k < 9; ++k) { ev[k] = -INFINITY; ei[k] = -1; }
-            for (int i = 0; i < n; ++i)
-                for (int k = 0; k < 9; ++k) {
-                    const double f = k < 8 ? qual_dir(k, uv[2 * i], uv[2 * i + 1])
-                                           : qual_radius(uv[2 * i], uv[2 * i + 1], prob->px_size[2 * c], prob->px_size[2 * c + 1],
-                                                         prob->IO_val[c * R + 1], prob->IO_val[c * R + 2]);
-                    if (ei[k] < 0 || f > ev[k]) { ev[k] = f; ei[k] = i; }
-                }
-            double eu[8], evv[8];
-            for (int k = 0; k < 8; ++k) { eu[k] = uv[2 * ei[k]]; evv[k] = uv[2 * ei[k] + 1]; }
-            l[0] = eu[0]; hh[0] = eu[4]; l[1] = evv[2]; hh[1] = evv[6];
-            rm = ev[8]; ri = i0 + ei[8];
-            QualOct oct;
-            qual_oct_build(eu, evv, hh[0] - l[0], hh[1] - l[1], oct);
-            idx.clear();
-            for (int i = 0; i < n; ++i) if (!qual_oct_inside(oct, uv[2 * i], uv[2 * i + 1])) idx.push_back(i);
-            const int ns = (int)idx.size();
-            const QualIdxPts p{uv, idx.data()};
-            std::sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) {        // the order of qual_less
-                if (uv[2 * a] != uv[2 * b]) return uv[2 * a] < uv[2 * b];
-                if (uv[2 * a + 1] != uv[2 * b + 1]) return uv[2 * a + 1] < uv[2 * b + 1];
-                return a < b;
-            });
-            stk.assign((size_t)ns + 1, 0);
-            h = qual_hull_chain(p, ns, stk.data());
-            area = qual_hull_area(p, stk.data(), h, l[0], l[1]);
-            if (hull_ip) for (int j = 0; j < h; ++j) hull_ip[nh + j] = i0 + idx[stk[j]];
-        }
-        nh += h;
-        if (lo) { lo[2 * c] = l[0]; lo[2 * c + 1] = l[1]; }
-        if (hi) { hi[2 * c] = hh[0]; hi[2 * c + 1] = hh[1]; }
-        if (rad_max) rad_max[c] = rm;
-        if (rad_ip) rad_ip[c] = ri;
-        if (hull_area) hull_area[c] = area;
-        if (hull_start) hull_start[c + 1] = nh;
-    }
     return DBAT_HIP_OK;
     API_CATCH
 }
@@ -3252,155 +2673,14 @@ int dbat_hip_resect(int32_t device, int32_t n_images, const int64_t *pt_start, c
     DevBuf<int64_t> dps, dts;
     DevBuf<double> dX, dx, dP, dr;
     DevBuf<int32_t> dtri;
-    dps.upload(std::vector<int64_t>(pt_start, pt_start + n_images + 1));
-    dts.upload(std::vector<int64_t>(tri_start, tri_start + n_images + 1));
-    dX.upload(std::vector<double>(X, X + 3 * npt)); dx.upload(std::vector<double>(xn, xn + 2 * npt));
-    dtri.upload(std::vector<int32_t>(tri, tri + 3 * ntri));
+    dps.upload(pt_start, (size_t)n_images + 1); dts.upload(tri_start, (size_t)n_images + 1);
+    dX.upload(X, (size_t)3 * npt); dx.upload(xn, (size_t)2 * npt); dtri.upload(tri, (size_t)3 * ntri);
     dP.alloc((size_t)12 * n_images); dr.alloc((size_t)n_images);
     launch<k_resect>(dim3((unsigned)n_images), dim3(64), 0, (hipStream_t)nullptr, n_images, dps.p, dX.p, dx.p, dts.p, dtri.p, 1, dP.p, dr.p);
     HIPCHK(hipMemcpy(P, dP.p, (size_t)12 * n_images * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(rms, dr.p, (size_t)n_images * sizeof(double), hipMemcpyDeviceToHost));
     return DBAT_HIP_OK;
     API_CATCH
-}
-
-/* ---- network transforms (align.hpp) ---- */
-
-int dbat_hip_rigidalign(int32_t device, int64_t n, const double *X, const double *Y, const uint8_t *use, int32_t scale,
-                        double *T, double *stats, double *resid) {
-    API_TRY
-    if (n < 0 || !T || !stats || (n > 0 && (!X || !Y))) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    // Everything that can be refused is refused here, before any device call.  The collinearity test needs the
-    // cross-product matrix: the host pass that looks at every used coordinate anyway also sums it, with the first used
-    // column as the origin of both sets.  The matrix the result comes from is the device's.
-    int64_t m = 0;
-    double x0[3] = {0, 0, 0}, y0[3] = {0, 0, 0}, Sx[3] = {0, 0, 0}, Sy[3] = {0, 0, 0}, Cxy[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t i = 0; i < n; ++i) {
-        if (use && !use[i]) continue;
-        const double *x = X + 3 * i, *y = Y + 3 * i;
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(x[k]) || !std::isfinite(y[k])) { g_err = "rigidalign: used column " + std::to_string(i) + " is not finite"; return DBAT_HIP_EINVAL; }
-        if (m++ == 0) for (int k = 0; k < 3; ++k) { x0[k] = x[k]; y0[k] = y[k]; }
-        double a[3], b[3];
-        for (int k = 0; k < 3; ++k) { a[k] = x[k] - x0[k]; b[k] = y[k] - y0[k]; Sx[k] += a[k]; Sy[k] += b[k]; }
-        for (int j = 0; j < 3; ++j) for (int k = 0; k < 3; ++k) Cxy[3 * j + k] += b[k] * a[j];
-    }
-    if (m < 3) { g_err = "rigidalign: fewer than three used columns"; return DBAT_HIP_EINVAL; }
-    {
-        double U[9], V[9], s[3];
-        for (int j = 0; j < 3; ++j) for (int k = 0; k < 3; ++k) Cxy[3 * j + k] -= Sy[k] * Sx[j] / (double)m;
-        al_svd3(Cxy, U, s, V);
-        if (!(s[1] > 1e-12 * s[0])) { g_err = ALIGN_COLLINEAR; return DBAT_HIP_EINVAL; }
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device: the dbat_hip core has no CPU path"; return DBAT_HIP_EDEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "bad device index"; return DBAT_HIP_EINVAL; }
-    DeviceGuard dev_guard(device);
-    const hipStream_t st = nullptr;
-    const int G = (int)al_grid(n);
-    DevBuf<double> dX, dY, part, out, dres;
-    DevBuf<uint8_t> duse;
-    upload_raw(dX, X, (size_t)3 * n); upload_raw(dY, Y, (size_t)3 * n);
-    if (use) upload_raw(duse, use, (size_t)n);
-    part.alloc((size_t)10 * G); out.alloc(18);
-    EventPair e0(g_align_timing), e1(g_align_timing), e2(g_align_timing);
-    e0.start();
-    launch<k_align_centroid>(dim3(G), dim3(AL_WG), 0, st, n, dX.p, dY.p, duse.p, part.p);
-    launch<k_align_finish<7, true>>(dim3(1), dim3(AL_WG), 0, st, G, part.p, out.p);
-    e0.stop();
-    e1.start();
-    launch<k_align_cross>(dim3(G), dim3(AL_WG), 0, st, n, dX.p, dY.p, duse.p, out.p, part.p);
-    launch<k_align_finish<10, false>>(dim3(1), dim3(AL_WG), 0, st, G, part.p, out.p + 7);
-    e1.stop();
-    double h[18];
-    HIPCHK(hipMemcpy(h, out.p, 17 * sizeof(double), hipMemcpyDeviceToHost));
-    g_align_ms[0] = e0.ms(); g_align_ms[1] = e1.ms(); g_align_ms[2] = g_align_ms[3] = g_align_ms[4] = 0;
-    // rigidalign.m:46-61
-    AlignPar ap;
-    double R[9], s[3];
-    al_rotation(h + 7, R, s);
-    if (!(s[1] > 1e-12 * s[0])) { g_err = ALIGN_COLLINEAR; return DBAT_HIP_EINVAL; }
-    double alpha = 1.0;
-    if (scale) {
-        double gamma = 0;                           // tr((R A)' B) = sum R_ij C_ij
-        for (int i = 0; i < 9; ++i) gamma += R[i] * h[7 + i];
-        alpha = gamma / h[16];
-    }
-    double d[3];
-    for (int k = 0; k < 3; ++k) { ap.xm[k] = h[1 + k]; ap.ym[k] = h[4 + k]; }
-    for (int i = 0; i < 9; ++i) { ap.aR[i] = alpha * R[i]; ap.aRl[i] = std::fma(alpha, R[i], -ap.aR[i]); }
-    for (int k = 0; k < 3; ++k) d[k] = ap.ym[k] - (ap.aR[k] * ap.xm[0] + ap.aR[3 + k] * ap.xm[1] + ap.aR[6 + k] * ap.xm[2]);
-    if (resid) dres.alloc((size_t)3 * n);
-    e2.start();
-    launch<k_align_resid>(dim3(G), dim3(AL_WG), 0, st, n, dX.p, dY.p, duse.p, ap, dres.p, part.p);
-    launch<k_align_finish<1, false>>(dim3(1), dim3(AL_WG), 0, st, G, part.p, out.p + 17);
-    e2.stop();
-    HIPCHK(hipMemcpy(h + 17, out.p + 17, sizeof(double), hipMemcpyDeviceToHost));
-    if (resid) HIPCHK(hipMemcpy(resid, dres.p, (size_t)3 * n * sizeof(double), hipMemcpyDeviceToHost));
-    g_align_ms[2] = e2.ms();
-    for (int j = 0; j < 3; ++j) {
-        for (int i = 0; i < 3; ++i) T[4 * j + i] = ap.aR[3 * j + i];
-        T[4 * j + 3] = 0; T[12 + j] = d[j];
-    }
-    T[15] = 1;
-    stats[0] = alpha; stats[1] = std::sqrt(h[17] / h[0]); stats[2] = h[0]; stats[3] = s[1] / s[0];
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_multixform(int32_t device, const double *T, int64_t n_images, int32_t eo_rows, double *EO, int64_t n_points,
-                        double *OP, uint8_t *fail) {
-    API_TRY
-    if (!T || n_images < 0 || n_points < 0 || (n_images > 0 && !EO) || (n_points > 0 && !OP)) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    if (eo_rows < 6) { g_err = "multixform: EO needs at least six rows"; return DBAT_HIP_EINVAL; }
-    XformPar par;
-    double alpha = 1.0;
-    if (const char *e = al_similarity(T, par, alpha)) { g_err = std::string("multixform: ") + e; return DBAT_HIP_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device: the dbat_hip core has no CPU path"; return DBAT_HIP_EDEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "bad device index"; return DBAT_HIP_EINVAL; }
-    DeviceGuard dev_guard(device);
-    const hipStream_t st = nullptr;
-    for (int i = 0; i < 5; ++i) g_align_ms[i] = 0;
-    if (n_points > 0) {
-        DevBuf<double> dOP;
-        upload_raw(dOP, (const double *)OP, (size_t)3 * n_points);
-        EventPair ev(g_align_timing);
-        ev.start();
-        launch<k_xform_points>(dim3((unsigned)cdiv(n_points, AL_WG)), dim3(AL_WG), 0, st, n_points, dOP.p, par);
-        ev.stop();
-        HIPCHK(hipMemcpy(OP, dOP.p, (size_t)3 * n_points * sizeof(double), hipMemcpyDeviceToHost));
-        g_align_ms[3] = ev.ms();
-    }
-    if (n_images > 0) {
-        DevBuf<double> dEO;
-        DevBuf<uint8_t> dfail;
-        upload_raw(dEO, (const double *)EO, (size_t)eo_rows * n_images);
-        dfail.alloc((size_t)n_images);
-        EventPair ev(g_align_timing);
-        ev.start();
-        launch<k_xform_cams>(dim3((unsigned)cdiv(n_images, AL_WG)), dim3(AL_WG), 0, st, n_images, (int)eo_rows, dEO.p, par, dfail.p);
-        ev.stop();
-        HIPCHK(hipMemcpy(EO, dEO.p, (size_t)eo_rows * n_images * sizeof(double), hipMemcpyDeviceToHost));
-        if (fail) HIPCHK(hipMemcpy(fail, dfail.p, (size_t)n_images, hipMemcpyDeviceToHost));
-        g_align_ms[4] = ev.ms();
-    }
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-/* Debug / measurement: dbat_hip_debug_align_timing(1) makes dbat_hip_rigidalign / dbat_hip_multixform on this thread
- * bracket their kernels with device events (off by default: a product call creates none); dbat_hip_debug_align_ms then
- * gives the milliseconds of the last call: ms[0] centroids, ms[1] cross products, ms[2] residuals, ms[3] points, ms[4]
- * cameras; each pass with its finishing launch; 0 for what the last call did not launch or did not time. */
-int dbat_hip_debug_align_timing(int32_t on) {
-    g_align_timing = on != 0;
-    return DBAT_HIP_OK;
-}
-int dbat_hip_debug_align_ms(double *ms) {
-    if (!ms) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    for (int i = 0; i < 5; ++i) ms[i] = g_align_ms[i];
-    return DBAT_HIP_OK;
 }
 
 int dbat_hip_chol_stats(const dbat_hip_handle *h, int64_t *st) {
@@ -3636,3 +2916,5 @@ int dbat_hip_debug_model_eval_host(int32_t model, int32_t nK, int32_t nP, const 
 }
 
 }  // extern "C"
+
+#include "align_host.hpp"         // the network transforms take no handle

@@ -120,6 +120,51 @@ def test_tiled_heavy_and_giant_points_and_a_real_project(hip, name):
                 assert np.array_equal(a[k], b[k], equal_nan=True)
 
 
+def same_bits(a, b):
+    """Two results of the same call (a dict or a tuple of arrays and numbers) are bit-equal, hulls list by list."""
+    a, b = (list(r.items()) if isinstance(r, dict) else list(enumerate(r)) for r in (a, b))
+    assert [k for k, _ in a] == [k for k, _ in b]
+    for (k, u), (_, v) in zip(a, b):
+        if k == 'hull':
+            assert len(u) == len(v) and all(np.array_equal(p, q) for p, q in zip(u, v))
+        else:
+            assert np.array_equal(u, v, equal_nan=True), k
+
+
+def test_the_analyses_share_one_point_index(hip):
+    """ray_angles and residual_stats take where every point's observations start, and which points are tiled or heavy,
+    from one index that the first of them builds: whichever call comes first on a handle, and whatever ran in between
+    (coverage, point_depths), every result has the same bits."""
+    s = thinned_scene()
+    calls = dict(coverage=lambda h, x: h.coverage(), angles=lambda h, x: h.ray_angles(x),
+                 stats=lambda h, x: h.residual_stats(x), depths=lambda h, x: h.point_depths(x))
+    runs = [('coverage', 'angles', 'stats', 'depths', 'angles', 'stats')]
+    runs += [(lead,) + tuple(k for k in calls if k != lead) for lead in ('angles', 'stats', 'depths')]
+    first = {}
+    for order in runs:
+        h = hip.Handle(s)
+        try:
+            info, x = h.info(), h.serialize()
+            got = [(k, calls[k](h, x)) for k in order]
+        finally:
+            h.close()
+        assert info['n_tiles'] > 0 and info['heavy_points'] >= 3          # both point kernels of both analyses run
+        for k, r in got:
+            same_bits(first.setdefault(k, r), r)
+    assert set(first) == set(calls)
+    # a point without a ray and a point with one, the statistics first
+    s = edge_scene()
+    h = hip.Handle(s)
+    try:
+        x = h.serialize()
+        st = h.residual_stats(x)
+        op, cam, opn, camn = h.ray_angles(x)
+    finally:
+        h.close()
+    assert opn[0] == 0 and opn[1] == 1 and np.array_equal(st['op_n'], opn)
+    assert np.isnan(op[0]) and op[1] == 0.0 and st['op_ss'][0] == 0.0
+
+
 def adjustable_thinned_scene():
     """thinned_scene() as a network that can be adjusted: an image with fewer than six points does not determine its
     six exterior parameters well, so those images keep their start values (every point still has two rays or more)."""
