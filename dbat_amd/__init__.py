@@ -10,7 +10,9 @@ Host-side mirror of the reference's interface for the bundle hot path:
                  rigidalign, multixform, multialign: misc/rigidalign.m, pm_multixform.m, pm_multialign.m on the device;
                  transform_network(s, T), align_network(s, ref_OP): a whole struct into another coordinate system
     loadpm       PhotoModeler export loader (known-answer fixtures)
-    initial      resect / forwintersect: initial EO and OP (photogrammetry/resect.m, forwintersect.m)
+    initial      resect / forwintersect: initial EO and OP (photogrammetry/resect.m, forwintersect.m);
+                 essmat5 / camsfrome / relorient / relorient_pairs: relative orientation of image pairs by a five-point
+                 RANSAC (photogrammetry/essmat5.m, camsfrome.m), for networks without control points or EO
     report       the result file (bundle_result_file.m)
     diagnose     post-mortem of rank-deficient problems (bundle.m:368-446)
     parallel     torch.distributed / RCCL plumbing for sharded object points

@@ -174,6 +174,9 @@ SYMBOLS = {
     'dbat_hip_resect': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, C.POINTER(C.c_int64), _ip, _dp, _dp]),
     'dbat_hip_rigidalign': (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _bp, C.c_int32, _dp, _dp, _dp]),
     'dbat_hip_multixform': (C.c_int, [C.c_int32, _dp, C.c_int64, C.c_int32, _dp, C.c_int64, _dp, _bp]),
+    'dbat_hip_essmat5': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, _dp, _ip]),
+    'dbat_hip_relorient': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, C.POINTER(C.c_int64), _ip, _dp,
+                                     C.c_int32, _dp, _dp, _ip, _bp, _bp, _dp]),
     'dbat_hip_bench_step': (C.c_int, [_H, C.c_double, C.c_int32, _dp]),
     'dbat_hip_structure_key': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_uint64)]),
     'dbat_hip_handle_key': (C.c_int, [_H, C.POINTER(C.c_uint64)]),
@@ -211,6 +214,8 @@ DEBUG_SYMBOLS = {
     'dbat_hip_debug_chirality_pass_ms': (C.c_int, [_H, _dp, C.c_int32, _dp]),
     'dbat_hip_debug_align_ms': (C.c_int, [_dp]),
     'dbat_hip_debug_align_timing': (C.c_int, [C.c_int32]),
+    'dbat_hip_debug_relorient_ms': (C.c_int, [_dp]),
+    'dbat_hip_debug_relorient_timing': (C.c_int, [C.c_int32]),
 }
 
 _lib = None
@@ -899,6 +904,78 @@ def resect_poses(pt_start, X, xn, tri_start, tri, device=0):
     check(lib.dbat_hip_resect(int(device), n, ps.ctypes.data_as(i64p), dptr(Xf), dptr(xf), ts.ctypes.data_as(i64p),
                               tf.ctypes.data_as(_ip), dptr(P), dptr(rms)))
     return P.reshape(n, 4, 3).transpose(0, 2, 1), rms
+
+
+def essmat5_sets(set_start, Q1, Q2, device=0):
+    """dbat_hip_essmat5 over the sets set_start[i] .. set_start[i + 1] of the columns of Q1, Q2 (3-by-total): (E (n, 10, 9),
+    n_sol (n)); E[i, k] is solution k of set i, sum E[i, k, a + 3 b] Q1[a] Q2[b] = 0, zero for k >= n_sol[i]."""
+    lib = load()
+    ss = np.ascontiguousarray(set_start, np.int64)
+    n = len(ss) - 1
+    Q1, Q2 = np.asarray(Q1, float), np.asarray(Q2, float)
+    if Q1.ndim != 2 or Q1.shape[0] != 3 or Q1.shape != Q2.shape or n < 0 or (n >= 0 and Q1.shape[1] != ss[-1]):
+        raise ValueError('essmat5: Q1 and Q2 must both be 3-by-n, n the end of the last set')
+    q1, q2 = _f64(Q1), _f64(Q2)
+    E, ns = np.zeros(90 * max(n, 1)), np.zeros(max(n, 1), np.int32)
+    check(lib.dbat_hip_essmat5(int(device), n, ss.ctypes.data_as(C.POINTER(C.c_int64)), dptr(q1), dptr(q2), dptr(E),
+                               ns.ctypes.data_as(_ip)))
+    return E[:90 * n].reshape(n, 10, 9), ns[:n]
+
+
+def relorient_pairs(pt_start, x1, x2, hyp_start, samples, thr2, front_dir, device=0):
+    """dbat_hip_relorient over the pairs pt_start[i] .. pt_start[i + 1] of the columns of x1, x2 (2-by-total) with the
+    samples hyp_start[i] .. hyp_start[i + 1] of the rows of samples (five indices local to the pair each) and the
+    thresholds thr2 (one per pair): dict(E (n, 9), P2 (n, 3, 4), stats (n, 8), inlier, in_front (total booleans),
+    X (3, total))."""
+    lib = load()
+    ps, hs = np.ascontiguousarray(pt_start, np.int64), np.ascontiguousarray(hyp_start, np.int64)
+    n = len(ps) - 1
+    x1, x2 = np.asarray(x1, float), np.asarray(x2, float)
+    smp = np.ascontiguousarray(np.asarray(samples, np.int32).reshape(-1, 5))
+    t2 = np.ascontiguousarray(np.broadcast_to(np.asarray(thr2, float), (max(n, 0),)))
+    if len(hs) != n + 1 or x1.ndim != 2 or x1.shape[0] != 2 or x1.shape != x2.shape or x1.shape[1] != ps[-1] or smp.shape[0] != hs[-1]:
+        raise ValueError('relorient: x1 and x2 must both be 2-by-n and samples k-by-5, n and k the ends of the last ranges')
+    total = x1.shape[1]
+    a, b = _f64(x1), _f64(x2)
+    E, P2, st = np.zeros(9 * max(n, 1)), np.zeros(12 * max(n, 1)), np.zeros(8 * max(n, 1), np.int32)
+    inl, fr, X = np.zeros(max(total, 1), np.uint8), np.zeros(max(total, 1), np.uint8), np.zeros(3 * max(total, 1))
+    i64p = C.POINTER(C.c_int64)
+    check(lib.dbat_hip_relorient(int(device), n, ps.ctypes.data_as(i64p), dptr(a), dptr(b), hs.ctypes.data_as(i64p),
+                                 smp.ctypes.data_as(_ip), dptr(t2), int(front_dir), dptr(E), dptr(P2), st.ctypes.data_as(_ip),
+                                 inl.ctypes.data_as(_bp), fr.ctypes.data_as(_bp), dptr(X)))
+    return dict(E=E[:9 * n].reshape(n, 9), P2=P2[:12 * n].reshape(n, 4, 3).transpose(0, 2, 1), stats=st[:8 * n].reshape(n, 8),
+                inlier=inl[:total].astype(bool), in_front=fr[:total].astype(bool), X=X[:3 * total].reshape(3, total, order='F'))
+
+
+def cams_from_e(e, x1, x2, front_dir, device=0):
+    """dbat_hip_relorient without samples (hyp_start NULL) for one pair and the given model e (9: sum e[a + 3 b] q1[a]
+    q2[b] = 0): dict(P2 (3, 4), X (3, n), in_front (n), sp (4))."""
+    lib = load()
+    x1, x2 = np.asarray(x1, float), np.asarray(x2, float)
+    if x1.ndim != 2 or x1.shape[0] != 2 or x1.shape != x2.shape:
+        raise ValueError('camsfrome: the points must be 2-by-n')
+    n = x1.shape[1]
+    ps = np.array([0, n], np.int64)
+    a, b, E, t2 = _f64(x1), _f64(x2), np.ascontiguousarray(np.asarray(e, float).reshape(9)).copy(), np.ones(1)
+    P2, st = np.zeros(12), np.zeros(8, np.int32)
+    inl, fr, X = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8), np.zeros(3 * max(n, 1))
+    check(lib.dbat_hip_relorient(int(device), 1, ps.ctypes.data_as(C.POINTER(C.c_int64)), dptr(a), dptr(b), None, None, dptr(t2),
+                                 int(front_dir), dptr(E), dptr(P2), st.ctypes.data_as(_ip), inl.ctypes.data_as(_bp),
+                                 fr.ctypes.data_as(_bp), dptr(X)))
+    return dict(P2=P2.reshape(4, 3).T.copy(), X=X[:3 * n].reshape(3, n, order='F'), in_front=fr[:n].astype(bool), sp=st[4:8].copy())
+
+
+def relorient_timing(on=True):
+    """Device events around the kernels of essmat5_sets / relorient_pairs calls on this thread (debug; off by default)."""
+    check(load().dbat_hip_debug_relorient_timing(int(bool(on))))
+
+
+def relorient_ms():
+    """Device-event milliseconds of the kernels of the last essmat5_sets / relorient_pairs call on this thread, after
+    relorient_timing(True) (debug)."""
+    ms = np.zeros(3)
+    check(load().dbat_hip_debug_relorient_ms(dptr(ms)))
+    return dict(solve=float(ms[0]), score=float(ms[1]), cams=float(ms[2]))
 
 
 def rigidalign(X, Y, scale=False, use=None, resid=False, device=0):

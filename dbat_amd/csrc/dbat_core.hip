@@ -29,6 +29,7 @@
 #include "depth.hpp"
 #include "quality.hpp"
 #include "align.hpp"
+#include "relorient.hpp"
 
 namespace dbat {
 
@@ -2918,3 +2919,4 @@ int dbat_hip_debug_model_eval_host(int32_t model, int32_t nK, int32_t nP, const 
 }  // extern "C"
 
 #include "align_host.hpp"         // the network transforms take no handle
+#include "relorient_host.hpp"     // nor does the relative orientation

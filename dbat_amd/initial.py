@@ -6,6 +6,10 @@ control points and forward intersection of the object points, on
                    built-ins around it: lens correction, the choice of the triangles, centre / angles from the
                    winning 3 x 4 matrix                                  (photogrammetry/resect.m:42-131)
   forwintersect -> dbat_hip_forwintersect (k_forwintersect)              (photogrammetry/forwintersect.m:19-46)
+  essmat5       -> dbat_hip_essmat5 (csrc/relorient.hpp k_essmat5)       (photogrammetry/essmat5.m:9-43)
+  camsfrome, relorient, relorient_pairs -> dbat_hip_relorient (k_essmat5, k_ro_score, k_ro_cams): relative orientation
+                   of image pairs without control points or EO -- a five-point RANSAC over samples drawn here, the
+                   camera pair and the points of the winner                (photogrammetry/camsfrome.m:16-59)
   largesttriangle (misc/largesttriangle.m:16-41), derotmat3d (photogrammetry/derotmat3d.m:17-19), rotmat3d (its inverse),
   lenscorr1 (bundle/cammodel/pm_multilenscorr1.m:45-69 + pm_lens1.m:36-72), cleareo, clearop (misc/)
 
@@ -178,6 +182,138 @@ def forwintersect(s0, ids='all', skipPrior=False, device=0):
     finally:
         h.close()
     return s
+
+# ---- relative orientation ----------------------------------------------------------------------------------------------
+
+def essmat5(Q1, Q2, device=0):
+    """EE = essmat5(Q1, Q2) (photogrammetry/essmat5.m): the essential matrices of n >= 5 correspondences, Q1 and Q2
+    3-by-n normalised homogeneous coordinates, as a 9-by-k array (k <= 10) of unit columns, on the device
+    (dbat_hip_essmat5).  Layout of the reference (essmat5.m:12-20): a column e satisfies
+    sum e[a + 3 b] Q1[a, i] Q2[b, i] = 0, so e.reshape(3, 3) (row-major) is the E with Q2' E Q1 = 0 -- the matrix
+    camsfrome(E, Q1, Q2, ...) expects.  Real solutions only, in ascending order of the root."""
+    from . import _hip
+    Q1 = np.asarray(Q1, float)
+    E, ns = _hip.essmat5_sets([0, Q1.shape[1] if Q1.ndim == 2 else 0], Q1, Q2, device=device)
+    return E[0, :ns[0]].T.copy()
+
+
+def camsfrome(E, x, xp, frontDir, device=0):
+    """[P1,P2,X,inFront,sp] = camsfrome(E, x, xp, frontDir) (photogrammetry/camsfrome.m): the camera pair [I | 0],
+    [R | t] (|t| = 1) of the 3-by-3 essential matrix E with xp' E x = 0, x and xp 3-by-n normalised homogeneous points in
+    image 1 and 2, the points X (4-by-n, homogeneous, in the frame of P1) by intersection of the rays, whether each is in
+    front of both cameras (frontDir = +1 / -1: the sign of z in front), and the sorted in-front counts sp of the four
+    candidates, on the device (dbat_hip_relorient with E as the only model: one sample is not drawn, E is scored as it
+    is).  A point of two parallel rays is never in front."""
+    from . import _hip
+    E, x, xp = np.asarray(E, float), np.asarray(x, float), np.asarray(xp, float)
+    if E.shape != (3, 3) or x.ndim != 2 or x.shape[0] != 3 or x.shape != xp.shape:
+        raise ValueError('camsfrome: E must be 3-by-3, x and xp 3-by-n')
+    r = _hip.cams_from_e(E.reshape(-1), x[:2] / x[2], xp[:2] / xp[2], int(np.sign(frontDir)), device=device)
+    n = x.shape[1]
+    return np.eye(3, 4), r['P2'], np.vstack([r['X'], np.ones((1, n))]), r['in_front'], r['sp']
+
+
+def draw_samples(n, n_hyp, rng):
+    """n_hyp rows of five distinct indices below n >= 5 from the generator rng: rows with a repeated index are drawn
+    again until none is left (n < 16: the head of a permutation per row)."""
+    n, n_hyp = int(n), int(n_hyp)
+    if n < 5:
+        raise ValueError('draw_samples: fewer than five correspondences')
+    if n < 16:
+        return np.array([rng.permutation(n)[:5] for _ in range(n_hyp)], np.int32).reshape(n_hyp, 5)
+    S = rng.integers(0, n, (n_hyp, 5))
+    while True:
+        srt = np.sort(S, 1)
+        bad = np.flatnonzero(np.any(srt[:, 1:] == srt[:, :-1], 1))
+        if bad.size == 0:
+            return S.astype(np.int32)
+        S[bad] = rng.integers(0, n, (bad.size, 5))
+
+
+def pair_points(s, i, j, xy=None):
+    """(pts, x1, x2) of the image pair (i, j), lens-corrected with lenscorr1 (xy: its result, if at hand): the object points seen in both images i and j (columns of OP, ascending) and their lens-corrected image points
+    normalised as resect() does: K \\ [x; y; 1] with -f, so that the cameras look along -z (frontDir = -1)."""
+    xy = lenscorr1(s) if xy is None else xy
+    ri, rj = np.flatnonzero(s.IP.cam == i), np.flatnonzero(s.IP.cam == j)
+    common, ai, aj = np.intersect1d(s.IP.pt[ri], s.IP.pt[rj], return_indices=True)
+    out = []
+    for cam, rows in ((i, ri[ai]), (j, rj[aj])):
+        IO = s.IO.val[:, cam]
+        out.append(np.stack([(xy[0, rows] - IO[1]) / -IO[0], (xy[1, rows] - IO[2]) / -IO[0]]))
+    return common, out[0], out[1]
+
+
+def pair_threshold(s, i, j, thr_px):
+    """thr_px pixels in normalised units: the mean over the two images of pixel size / focal length."""
+    u = [np.mean(s.IO.sensor.pxSize[:, c]) / abs(s.IO.val[0, c]) for c in (i, j)]
+    return float(thr_px) * 0.5 * (u[0] + u[1])
+
+
+def relorient_pairs(s, pairs, n_hyp=512, thr_px=3.0, seed=0, device=0):
+    """Relative orientation of the image pairs (i, j) of `pairs` in one device call (dbat_hip_relorient); s is not
+    touched.  Per pair the object points seen in both images are lens-corrected (lenscorr1) and normalised as resect()
+    does (with -f: the cameras look along -z, frontDir = -1), n_hyp samples of five are drawn with
+    np.random.default_rng(seed) (draw_samples, pair after pair from the one generator), and the RANSAC winner -- the
+    model with the most points whose Sampson distance is below thr_px pixels -- is decomposed.  There is no refit of the
+    winner on its inliers: bundle() is the refinement.  Returns a list of info per pair with
+      pts       the common object points (columns of s.OP.val)      samples   the samples drawn (n_hyp, 5)
+      E         3-by-3, x_j' E x_i = 0 (what camsfrome expects; the device returns the layout of essmat5, its transpose
+                as a column-major 3-by-3, and this function does the transposition)
+      P2        [R | t], |t| = 1: x_j ~ R X + t for X in the frame of image i       X   3-by-n, frame of image i
+      inlier, in_front   masks over pts      count     inliers      models    models scored
+      sample, sol        the winning sample (row of samples) and solution, -1 without one
+      sp        the four in-front counts, descending
+      ok        a model was found and sp[0] > sp[1] strictly
+    BadInput (ValueError) for a pair with fewer than five common points."""
+    from . import _hip
+    xy = lenscorr1(s)
+    rng = np.random.default_rng(seed)
+    pt_start, hyp_start, x1s, x2s, smps, thr2, pts = [0], [0], [], [], [], [], []
+    for i, j in pairs:
+        common, a, b = pair_points(s, int(i), int(j), xy)
+        if common.size < 5:
+            raise ValueError('relorient: images %d and %d share fewer than five points' % (i, j))
+        pts.append(common); x1s.append(a); x2s.append(b)
+        smps.append(draw_samples(common.size, n_hyp, rng))
+        thr2.append(pair_threshold(s, int(i), int(j), thr_px) ** 2)
+        pt_start.append(pt_start[-1] + common.size)
+        hyp_start.append(hyp_start[-1] + int(n_hyp))
+    if not pts:
+        return []
+    r = _hip.relorient_pairs(pt_start, np.concatenate(x1s, 1), np.concatenate(x2s, 1), hyp_start, np.concatenate(smps, 0),
+                             thr2, -1, device=device)
+    out = []
+    for k in range(len(pts)):
+        sl = slice(pt_start[k], pt_start[k + 1])
+        st = r['stats'][k]
+        out.append(dict(pts=pts[k], samples=smps[k], E=r['E'][k].reshape(3, 3).copy(), P2=r['P2'][k].copy(), X=r['X'][:, sl].copy(),
+                        inlier=r['inlier'][sl].copy(), in_front=r['in_front'][sl].copy(), count=int(st[0]), sample=int(st[1]),
+                        sol=int(st[2]), models=int(st[3]), sp=st[4:8].copy(), ok=bool(st[1] >= 0 and st[4] > st[5])))
+    return out
+
+
+def relorient(s0, i, j, n_hyp=512, thr_px=3.0, seed=0, device=0):
+    """Initial values for the image pair (i, j) of a network without control points or EO: (s, ok, info).  info is that
+    of relorient_pairs(s0, [(i, j)], ...).  In s -- a copy -- the EO of image i is the origin with zero angles, the EO of
+    image j comes from P2 = [R | t] (centre -R' t, a baseline of length one; omega, phi, kappa of R, as resect() takes
+    them), the OP of the common points in front of both cameras are their intersections X, and every other OP is NaN
+    (the frame is new: no other point has coordinates in it; forwintersect() fills them once more images are oriented).
+    The EO of the other images are left as they are.  ok = False, and s is s0 itself, when no sample gave a model or the
+    best of the four camera candidates does not have strictly more points in front than the next (sp[0] > sp[1]): a
+    pair without a baseline, for one."""
+    from .dbatstruct import copy_struct
+    info = relorient_pairs(s0, [(i, j)], n_hyp=n_hyp, thr_px=thr_px, seed=seed, device=device)[0]
+    if not info['ok']:
+        return s0, False, info
+    s = copy_struct(s0)
+    R, t = info['P2'][:, :3], info['P2'][:, 3]
+    s.EO.val[:6, i] = 0.0
+    s.EO.val[:3, j] = -R.T @ t
+    s.EO.val[3:6, j] = derotmat3d(R)
+    s.OP.val[:] = np.nan
+    f = info['in_front']
+    s.OP.val[:, info['pts'][f]] = info['X'][:, f]
+    return s, True, info
 
 
 resect_hip = resect                   # (names of rounds 2-3)

@@ -435,6 +435,69 @@ int  dbat_hip_rigidalign(int32_t device, int64_t n, const double *X, const doubl
 int  dbat_hip_multixform(int32_t device, const double *T, int64_t n_images, int32_t eo_rows, double *EO, int64_t n_points,
                          double *OP, uint8_t *fail);
 
+/* ---- relative orientation (additive to ABI 5; csrc/relorient.hpp) -------- */
+
+/* EE = essmat5(Q1, Q2) (photogrammetry/essmat5.m:9-43) for many sets of n >= 5 correspondences in one call, one lane
+ * per set.  No handle.
+ *   set_start [n_sets+1]   range of every set's correspondences in Q1 / Q2
+ *   Q1, Q2    [3*total]    normalised homogeneous coordinates K \ [x; y; 1], 3 per correspondence
+ *   E         [90*n_sets]  out: up to ten solutions per set, 9 doubles each, at unit norm and in the layout of
+ *                          essmat5.m:12-20: sum e[a + 3 b] Q1[a] Q2[b] = 0 (a, b = 0 .. 2); the slots past n_sol are zero
+ *   n_sol     [n_sets]     out: the number of solutions, 0 .. 10
+ * The design matrix (:12-20) is folded into a 9 x 9 triangle by Givens rotations, row after row, and the four right
+ * singular directions of smallest singular value (:23-24; for n = 5 the null space) come from one-sided Jacobi rotations
+ * of it -- what the eigenvectors of the Gram matrix give, without its squared condition number.  det E = 0 and
+ * 2 E E' E - tr(E E') E = 0 over E = x E1 + y E2 + z E3 + E4 are expanded by polynomial products in code (essmat5.m:45-856
+ * keeps the expanded form as tables), reduced with row pivoting (:27), and solved through the tenth-degree polynomial
+ * in z of Nister (2004) where :28-43 takes the eigenvalues of an action matrix: its real roots are bracketed between
+ * the roots of its derivative and bisected (a fixed number of steps; no complex arithmetic), and each solution is
+ * polished against the ten constraints evaluated on the matrix.  The solutions of a set are in ascending order of the
+ * root: two calls give the same bits.  Real roots only: :42 also keeps eigenvalues with |imag| / max |lambda| < 0.01 and
+ * takes their real part.  A set whose design matrix has rank below five (fifth singular value from below <= 1e-10 of the
+ * largest) or whose elimination meets a pivot <= 1e-13 of the largest coefficient has n_sol = 0; nothing returned is
+ * ever non-finite.
+ * DBAT_HIP_EINVAL, before any device call: a set of fewer than five; a coordinate that is not finite.  Then
+ * DBAT_HIP_EDEVICE without a HIP device (no CPU path). */
+int  dbat_hip_essmat5(int32_t device, int32_t n_sets, const int64_t *set_start, const double *Q1, const double *Q2,
+                      double *E, int32_t *n_sol);
+
+/* Relative orientation of n_pairs image pairs in one call: a RANSAC over the given minimal samples (essmat5.m per
+ * sample, as above), every model scored against every correspondence of its pair, and the camera pair and points of
+ * the winner, [P1,P2,X,inFront,sp] = camsfrome(E, x, xp, frontDir) (photogrammetry/camsfrome.m:16-59).  No handle.
+ *   pt_start  [n_pairs+1]  range of every pair's correspondences in x1 / x2
+ *   x1, x2    [2*total]    lens-corrected, normalised image coordinates K \ [x; y; 1] in image 1 and image 2 (the third
+ *                          coordinate, 1, is not stored)
+ *   hyp_start [n_pairs+1]  range of every pair's samples in samples
+ *   samples   [5*total]    five distinct indices into the pair's correspondences per sample: drawn by the caller, so
+ *                          the call is deterministic
+ *   thr2      [n_pairs]    inlier threshold on the squared Sampson distance, in normalised units; a correspondence is an
+ *                          inlier of e if r^2 < thr2 (|(M q2)(1:2)|^2 + |(M' q1)(1:2)|^2), r = q1' M q2, M[a][b] = e[a + 3 b]
+ *   front_dir              +1 / -1: the sign of z in front of the cameras (camsfrome.m:8)
+ *   E         [9*n_pairs]  out: the winner in the layout of dbat_hip_essmat5 (with q1 from x1, q2 from x2; read row-major
+ *                          it is the 3 x 3 matrix with x2' E x1 = 0 that camsfrome expects)
+ *   P2        [12*n_pairs] out: [R | t], |t| = 1, column-major 3 x 4, of the candidate of camsfrome.m:33 with the most
+ *                          points in front of both cameras (:55-57; of equal counts the first); camera 1 is [I | 0]
+ *   stats     [8*n_pairs]  out: the inlier count, the winning sample (local to the pair) and solution, the number of
+ *                          models scored, the four in-front counts in descending order (sp, :55-56)
+ *   inlier    [total]      out: 1 where the correspondence is an inlier of the returned E
+ *   in_front  [total]      out: 1 where the point is in front of both cameras (:49, :58)
+ *   X         [3*total]    out: the points in the frame of camera 1 (:59), every correspondence of the pair
+ * The winner has the highest inlier count; of equal counts the lowest (sample, solution) wins.  The 3 x 3 SVD of
+ * :16-22 is done on the host between launches.  A point is the middle of the common perpendicular of its two rays,
+ * which is what the normal equations of pm_forwintersect3.m:55-68 give for two rays; its depths (ptdepth.m:14) are
+ * X_z and (R X + t)_z.  Two rays closer to parallel than |d1 x d2|^2 = 1e-24 define no point: it is never in front
+ * (a pair without a baseline so gets sp = 0 0 0 0).  A pair for which no sample gave a model returns NaN in E, P2 and
+ * X, count 0, sample and solution -1 and all-zero masks.  No floating-point atomics: two calls give the same bits.
+ * hyp_start == NULL: E is an input as well, one model per pair in the layout above (camsfrome.m alone: nothing is
+ * sampled or scored; samples is not read; sample and solution are 0, the number of models 1).
+ * DBAT_HIP_EINVAL, before any device call: a pair of fewer than five correspondences; a coordinate that is not finite;
+ * a sample index out of range or repeated inside its sample; thr2 <= 0; front_dir not +-1; a given E that is not
+ * finite.  Then DBAT_HIP_EDEVICE
+ * without a HIP device (no CPU path). */
+int  dbat_hip_relorient(int32_t device, int32_t n_pairs, const int64_t *pt_start, const double *x1, const double *x2,
+                        const int64_t *hyp_start, const int32_t *samples, const double *thr2, int32_t front_dir,
+                        double *E, double *P2, int32_t *stats, uint8_t *inlier, uint8_t *in_front, double *X);
+
 /* ---- measurement hooks -------------------------------------------------- */
 
 /* One benchmark step = one Levenberg-Marquardt iteration's device work at
