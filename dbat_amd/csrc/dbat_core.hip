@@ -5,6 +5,7 @@
 #include <rocsolver/rocsolver.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -133,9 +134,9 @@ struct Core {
     int n_cu = 256;                  // compute units: launch size of the persistent tile kernel
     rocblas_handle blas = nullptr;
     // pinned host mailbox for the scalar read-backs of the damping loops (a copy to pageable memory is
-    // staged and costs a blit kernel of ~18 us each, seven per LM step): [0..31] scalars, [32..35]
-    // build sums, [40..47] pivots / info, [48..51] the pivot reset pattern
-    double *hpin = nullptr;
+    // staged and costs a blit kernel of ~18 us each, seven per LM step): MB_SIZE doubles, the slots MB_* of
+    // step_layout.hpp ("Step protocol": who writes and who reads each of them)
+    double *mailbox = nullptr;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t kev[13] = {};     // per-kernel brackets, recorded only while timing is on ([8], [9]: the all-reduce of the top tiles; [10 .. 12]: the kernels of the heavy / giant points)
     bool timing = false;
@@ -157,16 +158,15 @@ struct Core {
     int64_t sg_nchunks = 0;
     DevBuf<uint8_t> sg_lc;
     DevBuf<double> sg_uv, sg_w;
-    bool use_sig = false;
     int sig_rb = 4;
     int tile_ncx = 6;
     int64_t ntiles = 0;
     size_t lds_tile2 = 0, lds_tile3 = 0;
-    int tile2_pc = TILE2_PC;
-    bool use_tile2 = true;
-    // the kernel of the tiled batches, chosen once in init(): k_build_sig (signature groups, sig_rb row blocks),
-    // k_build_tile3 (fixed IO), k_build_tile2 (self-calibration), or none (nothing tiled)
+    // the kernel of the tiled batches, chosen once in init() and the only selector of it: k_build_sig (signature groups,
+    // sig_rb row blocks; the sg_* copies exist on this route alone), k_build_tile3 (fixed IO), k_build_tile2
+    // (self-calibration), or none (nothing tiled)
     enum class TileRoute { none, sig, tile3, tile2 } route = TileRoute::none;
+    template <class F> void with_model(F &&f) { with_value<2, 3, 4, 5>(P.model, f); }     // f(integral_constant): the lens model of the plan
     DevBuf<int64_t> o_row, batch_start, x2z, giant_start, cm_chunk_start;
     DevBuf<int32_t> cm_pt, cm_chunk_cam, tile_order;
     DevBuf<double> cm_uv, cm_w;
@@ -193,6 +193,20 @@ struct Core {
     // Vinv: six doubles per object point -- since round 3 the FACTOR R of the point block's inverse (V^-1 = R R',
     // kernels.hpp point_block_factor), not the inverse; gp: B'r per point; jn2p: squared column norms of the point columns
     DevBuf<double> jn2c, dscale, rhs, Vinv, gp, jn2p, partial, scal;
+    // Who writes where in `partial`, the per-workgroup sums that the tail kernels add up ("Step protocol"):
+    // layout_partial() fills it in init(), nothing else computes an offset into the buffer.
+    struct PartialLayout {
+        // a linearisation, one double per workgroup: the tile kernel from 0, then these; k_build_tail sums [0, total)
+        struct Build { int64_t lists, heavy, giants, total; };
+        Build build{}, build_det_lists{};   // ..._det_lists: deterministic mode off the signature route (no tile kernel)
+        // back-substitution, two doubles per workgroup: batch b at 2 b, then the giants, then k_backsub_sig's workgroups;
+        // k_prior_jv sums the bs_count pairs from bs_first on (batches before bs_first_batch belong to k_backsub_sig)
+        int64_t bs_giants = 0, bs_sig = 0, bs_first_batch = 0, bs_sig_wgs = 0, bs_first = 0, bs_count = 0;
+        // from 0: objective value and trace pass (one per camera-major chunk), J v (two per workgroup), dot products
+        int64_t n_cm_chunks_all = 0, grid_obs = 0, grid_z = 0;
+        int64_t doubles = 0;            // the allocation; end(): one past the last double that any user touches
+        int64_t end() const { return std::max({build.total, build_det_lists.total, bs_sig + 2 * bs_sig_wgs, n_cm_chunks_all, 2 * grid_obs, grid_z}); }
+    } part;
     DevBuf<int> info;
     DevBuf<double> linv, ldiag;
     DataflowChol dfchol;                // persistent task-graph Cholesky, cameras in nested-dissection order (chol_df.hpp)
@@ -255,7 +269,7 @@ struct Core {
         for (auto &e : kev) if (e) (void)hipEventDestroy(e);
         for (auto &e : st_ev) if (e) (void)hipEventDestroy(e);
         dfchol.release(); dfchol_ip.release();
-        if (hpin) (void)hipHostFree(hpin);
+        if (mailbox) (void)hipHostFree(mailbox);
         if (nccl) (void)ncclCommDestroy(nccl);
         if (blas) rocblas_destroy_handle(blas);
         if (stream) (void)hipStreamDestroy(stream);
@@ -280,12 +294,9 @@ struct Core {
         HIPCHK(hipStreamCreate(&stream));
         // coherent (fine-grained) on purpose: the kernels' stores must become visible to the spinning host
         // thread without a stream synchronisation, whatever HIP_HOST_COHERENT says
-        HIPCHK(hipHostMalloc((void **)&hpin, 64 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
-        memset(hpin, 0, 64 * sizeof(double));        // ticket slot 63 must not match the first wait by accident
-        {
-            const double big = 1e300;
-            memcpy(&hpin[48], &big, 8); hpin[49] = 0.0; memcpy(&hpin[50], &big, 8); hpin[51] = 0.0;   // bit patterns: min = 1e300, max = +0
-        }
+        HIPCHK(hipHostMalloc((void **)&mailbox, MB_SIZE * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+        memset(mailbox, 0, MB_SIZE * sizeof(double));        // the ticket (MB_TICKET) must not match the first wait by accident
+        for (int q = 0; q < MB_PIVOTS_N; q += 2) { mailbox[MB_PIVOT_RESET + q] = 1e300; mailbox[MB_PIVOT_RESET + q + 1] = 0.0; }   // bit patterns: min = 1e300, max = +0
         lapi("device, stream, pinned mailbox (the first call of a process initialises the HIP runtime: ~0.1 s)");
         for (auto &e : ev) HIPCHK(hipEventCreate(&e));
         for (auto &e : kev) HIPCHK(hipEventCreate(&e));
@@ -345,8 +356,16 @@ struct Core {
         d.tile_batch = tile_batch.p; d.tile_cam_start = tile_cam_start.p; d.tile_cams = tile_cams.p;
         d.tile_io_start = tile_io_start.p; d.tile_iocols = tile_iocols.p; d.tile_cam_io = tile_cam_io.p;
         tile_io_simple.upload(P.tile_io_simple); d.tile_io_simple = P.tile_io_simple.empty() ? nullptr : tile_io_simple.p;
-        use_sig = P.sg_ok && ntiles > 0 && tile_ncx <= 14;
-        if (use_sig) {
+        {   // the kernel of the tiled batches.  Signature groups where the plan has them; else the dense 128-row tiles: two producer
+            // groups for fixed IO (k_build_tile3 holds at most 64 batch offsets per tile, the plan's cap is 48), k_build_tile2 for self-calibration
+            const bool dense_ok = P.BT == 256 && P.ncolmax <= 15;      // (the plan does not tile anything else)
+            if (ntiles <= 0) route = TileRoute::none;
+            else if (P.sg_ok && tile_ncx <= 14) route = TileRoute::sig;
+            else if (dense_ok && !P.with_io && tile_ncx == 6) route = TileRoute::tile3;
+            else if (dense_ok && (tile_ncx == 14 || tile_ncx == 15)) route = TileRoute::tile2;
+            else throw DeviceError{"internal: tiles without a tile kernel"};
+        }
+        if (route == TileRoute::sig) {
             sg_chunk.upload(P.sg_chunk); sg_tile_chunk0.upload(P.sg_tile_chunk0); sg_lc.upload(P.sg_lc); sg_gcam.upload(P.sg_gcam);
             sg_nchunks = (int64_t)P.sg_chunk.size() / 8;
             sg_uv.upload(P.sg_uv);
@@ -410,37 +429,48 @@ struct Core {
         grid_obs = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(nobs, 256), env_grid_obs()));
         grid_z = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(P.NZ, 256), 2048));
         grid_zs = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(P.NZ, 2048), 256));
-        scal.alloc((size_t)16 + 4 * (size_t)P.nranks);
-        HIPCHK(hipMemset(scal.p, 0, ((size_t)16 + 4 * (size_t)P.nranks) * sizeof(double)));   // unused slots travel through the all-reduce
+        scal.alloc((size_t)scal_size(P.nranks));
+        HIPCHK(hipMemset(scal.p, 0, (size_t)scal_size(P.nranks) * sizeof(double)));   // unused slots travel through the all-reduce
         info.alloc(1);
         pivmm.alloc(4);
-        gctr.alloc(16); HIPCHK(hipMemset(gctr.p, 0, 16 * sizeof(unsigned)));
+        gctr.alloc(CTR_SIZE); HIPCHK(hipMemset(gctr.p, 0, CTR_SIZE * sizeof(unsigned)));
         rpart.alloc((size_t)grid_obs);
         gpart.alloc((size_t)8 * std::max<int64_t>(std::max<int64_t>(grid_z, cdiv(P.NS, 256)), 2048));
         lds_build = ((size_t)P.BT * P.ncolmax * 3 + (size_t)P.BT * 18) * sizeof(double);
         lds_back = (size_t)P.BT * 6 * sizeof(double);
         lds_cov = ((size_t)P.BT * P.ncolmax * 3 + (size_t)P.BT * 6) * sizeof(double);
         // wave-specialised tile kernel: 256-observation batches, 16-point chunks, 2 panels
-        tile2_pc = TILE2_PC;
         // per point of a batch (Plan::PMAX): tile2 B'B | B'r of two batches and V^-1 | g | R; tile3 both of two producer groups
         static_assert(Plan::PMAX == 256 / 2, "k_build_tile2 / k_build_tile3 lay out NPROD / 2 points per batch");
-        lds_tile2 = ((size_t)TILE2_NBUF * 3 * tile2_pc * TILE_LD + (size_t)2 * Plan::PMAX * 9 + (size_t)Plan::PMAX * 15 + TILE_LD) * sizeof(double);
+        lds_tile2 = ((size_t)TILE2_NBUF * 3 * TILE2_PC * TILE_LD + (size_t)2 * Plan::PMAX * 9 + (size_t)Plan::PMAX * 15 + TILE_LD) * sizeof(double);
         lds_tile3 = ((size_t)TILE3_NBUF * 3 * TILE3_PC * TILE_LD + (size_t)2 * Plan::PMAX * 9 + (size_t)2 * Plan::PMAX * 9 + TILE_LD) * sizeof(double);
-        use_tile2 = P.BT == 256 && P.ncolmax <= 15;      // (the plan does not tile anything else)
-        // fixed IO: the tile kernel with two producer groups (it holds at most 64 batch offsets per tile, the plan's
-        // cap is 48); self-calibration: k_build_tile2
-        if (ntiles <= 0) route = TileRoute::none;
-        else if (use_sig) route = TileRoute::sig;
-        else if (use_tile2 && !P.with_io && tile_ncx == 6) route = TileRoute::tile3;
-        else if (use_tile2 && (tile_ncx == 14 || tile_ncx == 15)) route = TileRoute::tile2;
-        else throw DeviceError{"internal: tiles without a tile kernel"};
-        partial.alloc((size_t)4 * std::max<int64_t>(std::max<int64_t>(std::max<int64_t>(nb + ntiles + ngiant + (int64_t)P.sg_chunk.size() / 8, n_cm_chunks_all), 2048), 1));
+        layout_partial();
+        partial.alloc((size_t)part.doubles);
         HIPCHK(hipMemcpy(z.p, P.z0.data(), P.NZ * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemset(dz.p, 0, P.NZ * 8));
         HIPCHK(hipMemset(zt.p, 0, P.NZ * 8));          // (entries of other ranks' domains are never written)
         precompute_image_side();
         HIPCHK(hipDeviceSynchronize());
         lapi("work arrays, image side");
+    }
+
+    // `partial` in one place: every user's offset and count, and the allocation that holds them all
+    void layout_partial() {
+        // tile_wgs workgroups of the tile kernel | column lists from batch b_lists0 on | k_heavy_z | giants
+        auto build_layout = [&](int64_t tile_wgs, int64_t b_lists0) {
+            const int64_t heavy = tile_wgs + (use_heavy ? P.nb_tiled : nb) - b_lists0, giants = heavy + (use_heavy ? nb - P.nb_tiled : 0);
+            return PartialLayout::Build{tile_wgs, heavy, giants, giants + ngiant};
+        };
+        part.build = build_layout(ntiles, P.nb_tiled);
+        part.build_det_lists = build_layout(0, 0);
+        const bool sig_bs = route == TileRoute::sig && P.sg_backsub_ok;
+        part.bs_first_batch = sig_bs ? P.nb_tiled : 0; part.bs_sig_wgs = sig_bs ? cdiv(sg_nchunks, 4) : 0;
+        part.bs_giants = 2 * nb; part.bs_sig = 2 * (nb + ngiant); part.bs_first = 2 * part.bs_first_batch;
+        part.bs_count = nb - part.bs_first_batch + ngiant + part.bs_sig_wgs;
+        part.n_cm_chunks_all = n_cm_chunks_all; part.grid_obs = grid_obs; part.grid_z = grid_z;
+        // every workgroup of a linearisation or a back-substitution at once, four doubles each; no less than 8192
+        part.doubles = 4 * std::max<int64_t>(std::max<int64_t>(nb + ntiles + ngiant + (int64_t)P.sg_chunk.size() / 8, n_cm_chunks_all), 2048);
+        if (part.end() > part.doubles) throw DeviceError{"internal: the partial sums of a step do not fit their buffer"};
     }
 
     // Fixed interior orientation: the image side of every observation once per handle (kernels.hpp k_uv_to_rhs).
@@ -452,10 +482,10 @@ struct Core {
         if (!uv_pre || nobs == 0) return;
         prep_cams(z.p, cams_f.p);                    // interior orientation: the fixed values
         if (!o_rhs.p) o_rhs.alloc((size_t)2 * nobs);
-        with_value<2, 3, 4, 5>(P.model, [&](auto M) {
+        with_model([&](auto M) {
             launch<k_uv_to_rhs<M>>(dim3((unsigned)cdiv(nobs, 256)), dim3(256), 0, d.nK, d.nP, cams_f.p, nobs, o_cam.p, o_uv.p, o_rhs.p);
             if (n_cm_chunks_all > 0) launch<k_uv_to_rhs_cm<M>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, d.nK, d.nP, cams_f.p, cm_chunk_cam.p, cm_chunk_start.p, cm_uv.p);
-            if (use_sig && sg_nchunks > 0) launch<k_uv_to_rhs_sig<M>>(dim3((unsigned)sg_nchunks), dim3(64), 0, d.nK, d.nP, cams_f.p, sg_chunk.p, sg_gcam.p, sg_uv.p);
+            if (route == TileRoute::sig && sg_nchunks > 0) launch<k_uv_to_rhs_sig<M>>(dim3((unsigned)sg_nchunks), dim3(64), 0, d.nK, d.nP, cams_f.p, sg_chunk.p, sg_gcam.p, sg_uv.p);
         });
         d.o_uv = o_rhs.p;
     }
@@ -475,7 +505,7 @@ struct Core {
             // fixed interior orientation with other values: the corrected image coordinates again, from the measured ones
             // (the camera-major and slot-major copies were converted in place)
             HIPCHK(hipMemcpy(cm_uv.p, P.cm_uv.data(), P.cm_uv.size() * 8, hipMemcpyHostToDevice));
-            if (use_sig && sg_nchunks > 0) HIPCHK(hipMemcpy(sg_uv.p, P.sg_uv.data(), P.sg_uv.size() * 8, hipMemcpyHostToDevice));
+            if (route == TileRoute::sig && sg_nchunks > 0) HIPCHK(hipMemcpy(sg_uv.p, P.sg_uv.data(), P.sg_uv.size() * 8, hipMemcpyHostToDevice));
             d.o_uv = o_uv.p;
             precompute_image_side();
             HIPCHK(hipStreamSynchronize(stream));
@@ -506,7 +536,7 @@ struct Core {
             return n;
         }
         // dense 128-row tiles: 36 lower-triangle blocks per k-step, chunks of PC points of every batch
-        const int pc = route == TileRoute::tile3 ? TILE3_PC : tile2_pc;
+        const int pc = route == TileRoute::tile3 ? TILE3_PC : TILE2_PC;
         for (int64_t b = 0; b < P.nb_tiled; ++b) {
             const int64_t o1 = P.batch_start[b + 1];
             const int npts = o1 > P.batch_start[b] ? (int)P.o_pidx[o1 - 1] + 1 : 0;
@@ -531,7 +561,7 @@ struct Core {
         // results ends in one (z_to_x / read_scal).
         bool done = false;
         if (mb_armed) {
-            volatile unsigned long long *slot = reinterpret_cast<volatile unsigned long long *>(hpin) + 63;
+            volatile unsigned long long *slot = reinterpret_cast<volatile unsigned long long *>(mailbox) + MB_TICKET;
             const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
             for (;;) {
                 for (int spin = 0; spin < 512 && !done; ++spin) { done = *slot == mb_seq; if (!done) cpu_relax(); }
@@ -544,16 +574,16 @@ struct Core {
         if (det_timeout_pending) {
             det_timeout_pending = false;
             unsigned n_to = 0;
-            memcpy(&n_to, hpin + 60, sizeof(unsigned));
+            memcpy(&n_to, mailbox + MB_DET_TIMEOUTS, sizeof(unsigned));
             if (n_to) {
-                HIPCHK(hipMemsetAsync(gctr.p + 7, 0, sizeof(unsigned), stream));
+                HIPCHK(hipMemsetAsync(gctr.p + CTR_SIG_TIMEOUTS, 0, sizeof(unsigned), stream));
                 throw DeviceError{"deterministic mode: " + std::to_string(n_to) + " chunk(s) of the signature kernel gave up waiting for their turn at "
                                   "the tile (spin cap): the sums of this linearisation are not order-fixed"};
             }
         }
         if (lin_pending) {      // trace(J'J): camera part from jn2c (estimated), point part from red_scal[1]
-            f_lin = 0.5 * hpin[32];
-            trace_jtj = hpin[34] + hpin[33];
+            f_lin = 0.5 * mailbox[MB_LIN_RR];
+            trace_jtj = mailbox[MB_LIN_TRACE_CAM] + mailbox[MB_LIN_TRACE_PT];
             lin_pending = false;
         }
     }
@@ -609,10 +639,10 @@ struct Core {
         return zgather.p;
     }
     void read_scal(double *host, int n) {
-        if (n <= 32) {
-            HIPCHK(hipMemcpyAsync(hpin, scal.p, n * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (n <= MB_SCAL_N) {
+            HIPCHK(hipMemcpyAsync(mailbox + MB_SCAL, scal.p, n * sizeof(double), hipMemcpyDeviceToHost, stream));
             sync();
-            memcpy(host, hpin, n * sizeof(double));
+            memcpy(host, mailbox + MB_SCAL, n * sizeof(double));
             return;
         }
         HIPCHK(hipMemcpyAsync(host, scal.p, n * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -700,21 +730,21 @@ struct Core {
         // the total to the pinned mailbox (one rank) or to scal[0] for the all-reduce.
         // small projects without prior observations: the residual kernel's last block sums up and tells the host itself
         const bool res_tail = n_cm_chunks_all > 0 && n_cm_chunks_all <= 512 && !d.any_prior && !multi() && !r_w_out && !r_unw_out;
-        with_value<2, 3, 4, 5>(P.model, [&](auto M) {
+        with_model([&](auto M) {
             with_value<false, true>(uv_pre, [&](auto PRE) {
-                if (n_cm_chunks_all > 0)
-                    launch<k_residual_cm<M, PRE>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, d, zz, cams_f.p, cm_pt.p, cm_uv.p, pw ? cm_w.p : (const double *)nullptr,
-                                                  cm_chunk_cam.p, cm_chunk_start.p, partial.p, res_tail ? gctr.p + 1 : (unsigned *)nullptr, scal.p, hpin, res_tail ? ++mb_seq : 0ull);
+                if (part.n_cm_chunks_all > 0)
+                    launch<k_residual_cm<M, PRE>>(dim3((unsigned)part.n_cm_chunks_all), dim3(256), 0, d, zz, cams_f.p, cm_pt.p, cm_uv.p, pw ? cm_w.p : (const double *)nullptr,
+                                                  cm_chunk_cam.p, cm_chunk_start.p, partial.p, res_tail ? gctr.p + CTR_OBJECTIVE : (unsigned *)nullptr, scal.p, mailbox, res_tail ? ++mb_seq : 0ull);
                 mark(7);
                 if (r_w_out || r_unw_out) launch<k_residual<M, PRE>>(dim3(grid_obs), dim3(256), 0, d, zz, cams_f.p, rpart.p, r_w_out, r_unw_out);
             });
         });
         if (!res_tail)
-            launch<k_prior_sq>(dim3(grid_zs), dim3(1024), 0, d, zz, gpart.p, gctr.p + 1, (const double *)partial.p, n_cm_chunks_all,
-                               scal.p, multi() ? (double *)nullptr : hpin, ++mb_seq);
+            launch<k_prior_sq>(dim3(grid_zs), dim3(1024), 0, d, zz, gpart.p, gctr.p + CTR_OBJECTIVE, (const double *)partial.p, part.n_cm_chunks_all,
+                               scal.p, multi() ? (double *)nullptr : mailbox, ++mb_seq);
         double s;
         if (multi()) { do_allreduce(scal.p, 1); read_scal(&s, 1); }
-        else { mb_armed = true; sync(); s = hpin[0]; }
+        else { mb_armed = true; sync(); s = mailbox[MB_OBJECTIVE]; }
         ++n_res_evals;
         return 0.5 * s;
     }
@@ -759,14 +789,15 @@ struct Core {
         d.det_cam_part = det_cam_part.p; d.det_io_part = det_io_part.p; d.det_rr = det_rr.p; d.det_u = det_u.p;
         d.det_cam_chunks = det_cam_chunks.p;
     }
-    // the camera side of a deterministic linearisation, after the camera-major kernel has left its chunk partials
-    const double *det_z = nullptr;      // the point of the deterministic linearisation in progress
-    void det_camera_side() {
+    // the camera side of a deterministic linearisation at zz: EVERY observation (tiled or not) through the camera-major
+    // kernels, then their chunk partials summed in order
+    void det_camera_side_enqueue(const double *zz) {
         const int nio = (int)P.nIOu;
         const int ncx = det_ncx();
+        cam_normal(zz, 0, n_cm_chunks_all, ncx);
         with_value<6, 14, 15>(ncx, [&](auto NCX) { launch<k_det_cam_reduce<NCX>>(dim3((unsigned)P.nc), dim3(256), 0, d, cams.p, S, g_c, g_red, diagU); });
         if (ncx > 6 && nio > 0) launch<k_det_io_reduce<15>>(dim3((unsigned)(nio * (nio + 1) / 2 + nio)), dim3(256), 0, d, cams.p, nio, S, g_c, g_red, diagU);
-        if (d.any_prior) launch<k_det_prior_sq>(dim3(DET_PRIOR_PARTS), dim3(256), 0, d, det_z);
+        if (d.any_prior) launch<k_det_prior_sq>(dim3(DET_PRIOR_PARTS), dim3(256), 0, d, zz);
         launch<k_det_rows>(dim3((unsigned)cdiv(P.NS, 256)), dim3(256), 0, d, (const double *)diagU);
         if (ncx == 6) launch<k_det_round_cam<6>>(dim3((unsigned)P.nc), dim3(256), 0, d, cams.p, 0, S, g_red);
         else launch<k_det_round_cam<15>>(dim3((unsigned)P.nc + 1), dim3(256), 0, d, cams.p, nio, S, g_red);
@@ -775,7 +806,7 @@ struct Core {
     // camera side J_c'J_c, J_c'r and squared column norms of the camera-major chunks [q0, q0 + nq)
     void cam_normal(const double *zz, int64_t q0, int64_t nq, int ncx) {
         const double *w = pw ? cm_w.p : (const double *)nullptr;
-        with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15>(ncx, [&](auto NCX) {
+        with_model([&](auto M) { with_value<6, 14, 15>(ncx, [&](auto NCX) {
             if constexpr (NCX == 6)
                 launch<k_cam_normal6<M>>(dim3((unsigned)nq), dim3(256), 0, d, zz, cams.p, cm_pt.p, cm_uv.p, w, cm_chunk_cam.p + q0, cm_chunk_start.p + q0, S, g_c, g_red, diagU);
             else
@@ -783,145 +814,125 @@ struct Core {
         }); });
     }
 
-    // ---- K1: linearise at zz with damping lambda; builds the reduced system.
-    void build_enqueue(const double *zz, double lambda, int scale) {
-        stage(0);
-        const bool fused_first = !s_dense_dirty && P.NS >= P.nc;
-        if (!fused_first) prep_cams(zz);
-        else cams_at_lin = false;
-        // only the envelope of S is ever written or read: zero that (and the vectors behind S); the whole
-        // array once, and again after something filled it densely (the inverse of the posterior covariance)
-        bool pivmm_set = false;
+    // ---- K1: linearise at zz with damping lambda; builds the reduced system.  build_enqueue() is the list of its steps.
+    // only the envelope of S is ever written or read: zero that (and the vectors behind S); the whole
+    // array once, and again after something filled it densely (the inverse of the posterior covariance)
+    void clear_system_enqueue(const double *zz) {
+        if (s_dense_dirty || P.NS < P.nc) prep_cams(zz);
+        else cams_at_lin = false;                    // (k_envelope_cams has a block per camera: it makes the records)
         if (s_dense_dirty) {
             HIPCHK(hipMemsetAsync(red.p, 0, red_count * sizeof(double), stream));
             s_dense_dirty = false;
-        } else {
-            // ... and the vectors behind S, and the pivot extremes {min, max} x {points, cameras}
-            // ... and the camera records at zz, all in the first launch
+            HIPCHK(hipMemcpyAsync(pivmm.p, mailbox + MB_PIVOT_RESET, MB_PIVOTS_N * sizeof(double), hipMemcpyHostToDevice, stream));
+        } else {     // ... and the vectors behind S, the pivot extremes {min, max} x {points, cameras}, the camera records at zz
             launch<k_envelope_cams>(dim3((unsigned)P.NS), dim3(256), 0, d, zz, cams.p, S, ldS, (int)P.NS, env_tail0, col_bend.p, g_red, pivmm.p);
-            pivmm_set = true;
         }
-        if (!pivmm_set) HIPCHK(hipMemcpyAsync(pivmm.p, hpin + 48, 4 * sizeof(double), hipMemcpyHostToDevice, stream));
-        // tiled batches through the MFMA kernel, the remaining ("heavy point") batches
-        // -- or all of them when tiling is off -- through k_build
-        int64_t npart = 0;
-        // deterministic mode off the signature path: no tile kernel, k_build takes every batch
-        const bool det_list = deterministic && route != TileRoute::sig;
-        const int64_t nb_tiled = det_list ? 0 : P.nb_tiled;
-        if (deterministic) {
-            // the camera side of EVERY observation (tiled or not) from the camera-major kernels, chunk partials summed in order
-            cam_normal(zz, 0, n_cm_chunks_all, det_ncx());
-            det_z = zz;
-            det_camera_side();
-        }
-        if (ntiles > 0 && nb_tiled > 0) {
-            npart = ntiles;
-            // camera side of the tiled observations: J_c'J_c, J_c'r, squared column norms
-            if (!deterministic && use_tile2 && tile_ncx <= 15 && n_cm_chunks > 0) cam_normal(zz, 0, n_cm_chunks, tile_ncx);
-            mark(0);                                 // events around the tile kernel alone (bench roofline)
-            with_value<2, 3, 4, 5>(P.model, [&](auto M) {
-                if (route == TileRoute::sig) {
-                    with_value<6, 14>(tile_ncx, [&](auto NCX) { with_value<4, 5>(sig_rb, [&](auto RB) { with_value<false, true>(pw, [&](auto PW) {
-                        launch<k_build_sig<M, RB, NCX, PW>>(dim3((unsigned)std::min<int64_t>(ntiles, n_cu)), dim3(64 * sig_waves(RB, NCX > 6)), sig_lds_bytes(RB, NCX > 6),
-                                                            d, zz, cams.p, lambda, scale, S, g_red, Vinv.p, gp.p, jn2p.p, partial.p, pivmm.p, sg_chunk.p, sg_tile_chunk0.p,
-                                                            sg_lc.p, sg_uv.p, PW ? sg_w.p : (const double *)nullptr, gctr.p + 5);
-                    }); }); });
-                } else if (route == TileRoute::tile3) {
-                    launch<k_build_tile3<M, TILE3_PC, TILE3_NBUF>>(dim3((unsigned)ntiles), dim3(768), lds_tile3, d, zz, cams.p, lambda, scale, S, g_red, Vinv.p, gp.p,
-                                                                   jn2p.p, partial.p, pivmm.p);
-                } else {
-                    with_value<14, 15>(tile_ncx, [&](auto NCX) {
-                        launch<k_build_tile2<M, NCX, TILE2_PC, TILE2_NBUF>>(dim3((unsigned)ntiles), dim3(512), lds_tile2, d, zz, cams.p, lambda, scale, S, g_c, g_red,
-                                                                            diagU, Vinv.p, gp.p, jn2p.p, partial.p, pivmm.p);
-                    });
-                }
-            });
-            mark(1);
-        }
-        const bool no_tiles = !(ntiles > 0 && nb_tiled > 0);
-        if (no_tiles) mark(0);                       // no tile kernel: the events bracket the kernels of the untiled points instead
-        // heavy.hpp: the untiled points -- batches [P.nb_tiled, nb) and the giant points -- on the matrix cores; the
-        // tiled batches that the deterministic mode keeps off the tile kernels stay with the column lists
-        const int64_t nb_lists = use_heavy ? P.nb_tiled : nb;      // batches [nb_tiled, nb_lists) go through k_build
-        if (nb_lists > nb_tiled) {
-            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
-                launch<k_build<M, IO>>(dim3((unsigned)(nb_lists - nb_tiled)), dim3(P.BT), lds_build, d, zz, cams.p, lambda, scale, S, g_c, g_red, diagU, Vinv.p, gp.p,
-                                       jn2p.p, partial.p + npart, pivmm.p, (int)nb_tiled);
-            }); });
-            npart += nb_lists - nb_tiled;
-        }
-        if (use_heavy) {
-            mark(10);
-            // camera side of the untiled observations (deterministic mode: every chunk has been through it above)
-            if (!deterministic && n_cm_chunks_all > n_cm_chunks) cam_normal(zz, n_cm_chunks, n_cm_chunks_all - n_cm_chunks, tile_ncx);
-            if (nb > P.nb_tiled) {
-                with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15>(tile_ncx, [&](auto NCX) {
-                    launch<k_heavy_z<M, NCX>>(dim3((unsigned)(nb - P.nb_tiled)), dim3(256), heavy_z_lds_bytes(NCX, P.hv_max_batch_slots, deterministic), d, hv, zz,
-                                              cams.p, lambda, scale, hv_Z.p, Vinv.p, gp.p, jn2p.p, partial.p + npart, pivmm.p, (int)P.nb_tiled);
-                }); });
-                npart += nb - P.nb_tiled;
+    }
+    // the tiled batches through the MFMA kernel of the route; its workgroups' sums go to partial[0 .. ntiles)
+    void tiled_points_enqueue(const double *zz, double lambda, int scale) {
+        // camera side of the tiled observations: J_c'J_c, J_c'r, squared column norms
+        if (!deterministic && n_cm_chunks > 0) cam_normal(zz, 0, n_cm_chunks, tile_ncx);
+        mark(0);                                 // events around the tile kernel alone (bench roofline)
+        with_model([&](auto M) {
+            if (route == TileRoute::sig) {
+                with_value<6, 14>(tile_ncx, [&](auto NCX) { with_value<4, 5>(sig_rb, [&](auto RB) { with_value<false, true>(pw, [&](auto PW) {
+                    launch<k_build_sig<M, RB, NCX, PW>>(dim3((unsigned)std::min<int64_t>(ntiles, n_cu)), dim3(64 * sig_waves(RB, NCX > 6)), sig_lds_bytes(RB, NCX > 6),
+                                                        d, zz, cams.p, lambda, scale, S, g_red, Vinv.p, gp.p, jn2p.p, partial.p, pivmm.p, sg_chunk.p, sg_tile_chunk0.p,
+                                                        sg_lc.p, sg_uv.p, PW ? sg_w.p : (const double *)nullptr, gctr.p + CTR_SIG_TICKET);
+                }); }); });
+            } else if (route == TileRoute::tile3) {
+                launch<k_build_tile3<M, TILE3_PC, TILE3_NBUF>>(dim3((unsigned)ntiles), dim3(768), lds_tile3, d, zz, cams.p, lambda, scale, S, g_red, Vinv.p, gp.p, jn2p.p, partial.p, pivmm.p);
+            } else {
+                with_value<14, 15>(tile_ncx, [&](auto NCX) {
+                    launch<k_build_tile2<M, NCX, TILE2_PC, TILE2_NBUF>>(dim3((unsigned)ntiles), dim3(512), lds_tile2, d, zz, cams.p, lambda, scale, S, g_c, g_red,
+                                                                        diagU, Vinv.p, gp.p, jn2p.p, partial.p, pivmm.p);
+                });
             }
-            if (ngiant > 0) {
-                with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15>(tile_ncx, [&](auto NCX) {
-                    launch<k_heavy_z_giant<M, NCX>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, hv, zz, cams.p, lambda, scale, hv_Z.p, Vinv.p, gp.p, jn2p.p,
-                                                    partial.p + npart, pivmm.p);
-                }); });
-                npart += ngiant;
-            }
-            mark(11);
-            launch<k_heavy_syrk>(dim3((unsigned)cdiv(hv.ntasks, 4)), dim3(256), 0, d, hv, (const double *)hv_Z.p, S, g_red);
-            mark(12);
-        }
-        if (no_tiles) mark(1);
-        if (ngiant > 0 && !use_heavy) {               // points with more observations than a batch holds
-            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
-                launch<k_build_giant<M, IO>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, zz, cams.p, lambda, scale, S, g_c, g_red, diagU, Vinv.p, gp.p, jn2p.p,
-                                             partial.p + npart, pivmm.p);
+        });
+        mark(1);
+    }
+    // the batches [b0, b1) by the column lists (k_build)
+    void list_points_enqueue(const double *zz, double lambda, int scale, int64_t b0, int64_t b1, int64_t part0) {
+        with_model([&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
+            launch<k_build<M, IO>>(dim3((unsigned)(b1 - b0)), dim3(P.BT), lds_build, d, zz, cams.p, lambda, scale, S, g_c, g_red, diagU, Vinv.p, gp.p,
+                                   jn2p.p, partial.p + part0, pivmm.p, (int)b0);
+        }); });
+    }
+    // heavy.hpp: the untiled points -- batches [P.nb_tiled, nb) and the giant points -- on the matrix cores
+    void heavy_points_enqueue(const double *zz, double lambda, int scale, const PartialLayout::Build &pl) {
+        mark(10);
+        // camera side of the untiled observations (deterministic mode: every chunk has been through it above)
+        if (!deterministic && n_cm_chunks_all > n_cm_chunks) cam_normal(zz, n_cm_chunks, n_cm_chunks_all - n_cm_chunks, tile_ncx);
+        if (nb > P.nb_tiled)
+            with_model([&](auto M) { with_value<6, 14, 15>(tile_ncx, [&](auto NCX) {
+                launch<k_heavy_z<M, NCX>>(dim3((unsigned)(nb - P.nb_tiled)), dim3(256), heavy_z_lds_bytes(NCX, P.hv_max_batch_slots, deterministic), d, hv, zz,
+                                          cams.p, lambda, scale, hv_Z.p, Vinv.p, gp.p, jn2p.p, partial.p + pl.heavy, pivmm.p, (int)P.nb_tiled);
             }); });
-            npart += ngiant;
-        }
-        if (deterministic && route == TileRoute::sig && !no_tiles) {
-            // deterministic mode: chunks whose turn at the tile never came (sig.hpp, spin cap) -- read with the scalars
-            HIPCHK(hipMemcpyAsync(hpin + 60, gctr.p + 7, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-            det_timeout_pending = true;
-        }
-        if ((d.ablate & 32) && use_heavy && nb > P.nb_tiled) {      // phase profile of k_heavy_z (thread 0 of every batch)
-            unsigned long long h[16];
-            HIPCHK(hipStreamSynchronize(stream));
-            HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tile2_prof), sizeof(h)));
-            static const char *nm[6] = {"evaluate", "V, g sums", "point blocks", "EO rows of Z", "IO rows of Z", "tail"};
-            fprintf(stderr, "[heavy_z prof, us per batch (thread 0) avg over %d batches]", (int)(nb - P.nb_tiled));
-            for (int i = 0; i < 6; ++i) fprintf(stderr, " %s=%.2f", nm[i], h[8 + i] * 0.01 / (double)std::max<int64_t>(nb - P.nb_tiled, 1));
-            fprintf(stderr, "\n");
-            for (int i = 8; i < 16; ++i) h[i] = 0;
-            HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_tile2_prof), h, sizeof(h)));
-        }
-        if ((d.ablate & 32) && use_sig) {            // phase profile of the signature kernel (wave 0 of every tile)
-            unsigned long long h[16];
-            HIPCHK(hipStreamSynchronize(stream));
-            HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tile2_prof), sizeof(h)));
-            static const char *nm[8] = {"tile init", "chunk head", "pass 1", "pass 2 eval+write", "pass 2 mfma", "chunk flush", "wait for the tile", "tile flush"};
-            fprintf(stderr, "[sig prof, us per tile (wave 0) avg over %d tiles]", (int)ntiles);
-            for (int i = 0; i < 8; ++i) fprintf(stderr, " %s=%.2f", nm[i], h[i] * 0.01 / (double)std::max<int64_t>(ntiles, 1));
-            fprintf(stderr, "\n");
-            memset(h, 0, sizeof(h));
-            HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_tile2_prof), h, sizeof(h)));
-        } else if ((d.ablate & 32) && use_tile2) {   // phase profile of the wave-specialised tile kernel
-            unsigned long long h[16];
-            HIPCHK(hipStreamSynchronize(stream));
-            HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tile2_prof), sizeof(h)));
-            static const char *nm[12] = {"stage(wait freed)", "P1", "pbarrier", "P2", "P3", "drain", "cons wait full", "cons zero+free", "tail/flush", "loop head", "cons product", "cons wait done"};
-            fprintf(stderr, "[tile2 prof, us per tile avg over %d tiles]", (int)ntiles);
-            for (int i = 0; i < 12; ++i) fprintf(stderr, " %s=%.2f", nm[i], h[i] * 0.01 / (double)std::max<int64_t>(ntiles, 1));
-            fprintf(stderr, "\n");
-            memset(h, 0, sizeof(h));
-            HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_tile2_prof), h, sizeof(h)));
-        }
-        // red_scal[0] = the build kernels' residual sums + the prior rows' squares, red_scal[1] = owned
-        // squared column norms of the point columns
-        // (and keeps the copy of zz that the solve works from)
-        launch<k_build_tail>(dim3(grid_zs), dim3(1024), 0, d, zz, partial.p, npart, jn2p.p, gpart.p, gctr.p + 2, red_scal,
+        if (ngiant > 0)
+            with_model([&](auto M) { with_value<6, 14, 15>(tile_ncx, [&](auto NCX) {
+                launch<k_heavy_z_giant<M, NCX>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, hv, zz, cams.p, lambda, scale, hv_Z.p, Vinv.p, gp.p, jn2p.p,
+                                                partial.p + pl.giants, pivmm.p);
+            }); });
+        mark(11);
+        launch<k_heavy_syrk>(dim3((unsigned)cdiv(hv.ntasks, 4)), dim3(256), 0, d, hv, (const double *)hv_Z.p, S, g_red);
+        mark(12);
+    }
+    // points with more observations than a batch holds, by the column lists
+    void giants_enqueue(const double *zz, double lambda, int scale, int64_t part0) {
+        with_model([&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
+            launch<k_build_giant<M, IO>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, zz, cams.p, lambda, scale, S, g_c, g_red, diagU, Vinv.p, gp.p, jn2p.p,
+                                         partial.p + part0, pivmm.p);
+        }); });
+    }
+    // deterministic mode: chunks whose turn at the tile never came (sig.hpp, spin cap) -- read with the scalars
+    void det_timeouts_enqueue() {
+        HIPCHK(hipMemcpyAsync(mailbox + MB_DET_TIMEOUTS, gctr.p + CTR_SIG_TIMEOUTS, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        det_timeout_pending = true;
+    }
+    // red_scal[0] = the build kernels' npart residual sums + the prior rows' squares, red_scal[1] = owned squared
+    // column norms of the point columns (and keeps the copy of zz that the solve works from)
+    void build_tail_enqueue(const double *zz, int64_t npart) {
+        launch<k_build_tail>(dim3(grid_zs), dim3(1024), 0, d, zz, partial.p, npart, jn2p.p, gpart.p, gctr.p + CTR_BUILD_TAIL, red_scal,
                 zz != zlin.p ? zlin.p : (double *)nullptr);
+    }
+    // measurement build (ablation bit 32): the phase clocks g_tile2_prof[first, first + count), averaged over n workgroups; clears from first on
+    void dump_phase_profile(const char *title, const char *unit, const char *const *names, int first, int count, int64_t n) {
+        unsigned long long h[16];
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_tile2_prof), sizeof(h)));
+        fprintf(stderr, "[%s avg over %d %s]", title, (int)n, unit);
+        for (int i = 0; i < count; ++i) fprintf(stderr, " %s=%.2f", names[i], h[first + i] * 0.01 / (double)std::max<int64_t>(n, 1));
+        fprintf(stderr, "\n");
+        for (int i = first; i < 16; ++i) h[i] = 0;
+        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_tile2_prof), h, sizeof(h)));
+    }
+    void dump_phase_profiles() {
+        static const char *const heavy[6] = {"evaluate", "V, g sums", "point blocks", "EO rows of Z", "IO rows of Z", "tail"};
+        static const char *const sig[8] = {"tile init", "chunk head", "pass 1", "pass 2 eval+write", "pass 2 mfma", "chunk flush", "wait for the tile", "tile flush"};
+        static const char *const tile2[12] = {"stage(wait freed)", "P1", "pbarrier", "P2", "P3", "drain", "cons wait full", "cons zero+free", "tail/flush", "loop head", "cons product", "cons wait done"};
+        if (use_heavy && nb > P.nb_tiled) dump_phase_profile("heavy_z prof, us per batch (thread 0)", "batches", heavy, 8, 6, nb - P.nb_tiled);
+        if (route == TileRoute::sig) dump_phase_profile("sig prof, us per tile (wave 0)", "tiles", sig, 0, 8, ntiles);
+        else if (route != TileRoute::none) dump_phase_profile("tile2 prof, us per tile", "tiles", tile2, 0, 12, ntiles);
+    }
+    void build_enqueue(const double *zz, double lambda, int scale) {
+        stage(0);
+        // deterministic mode off the signature route: no tile kernel (its per-point sums are LDS atomics from several
+        // waves), the column lists take the tiled batches too
+        const bool det_lists = deterministic && route != TileRoute::sig;
+        const bool tiles = route != TileRoute::none && !det_lists;
+        const PartialLayout::Build &pl = det_lists ? part.build_det_lists : part.build;
+        const int64_t b_lists0 = det_lists ? 0 : P.nb_tiled, b_lists1 = use_heavy ? P.nb_tiled : nb;
+        clear_system_enqueue(zz);
+        if (deterministic) det_camera_side_enqueue(zz);
+        if (tiles) tiled_points_enqueue(zz, lambda, scale);
+        else mark(0);                                // no tile kernel: the events bracket the kernels of the untiled points instead
+        if (b_lists1 > b_lists0) list_points_enqueue(zz, lambda, scale, b_lists0, b_lists1, pl.lists);
+        if (use_heavy) heavy_points_enqueue(zz, lambda, scale, pl);
+        if (!tiles) mark(1);
+        if (ngiant > 0 && !use_heavy) giants_enqueue(zz, lambda, scale, pl.giants);
+        if (deterministic && tiles) det_timeouts_enqueue();      // (the signature route: the only tile kernel of this mode)
+        if (d.ablate & 32) dump_phase_profiles();
+        build_tail_enqueue(zz, pl.total);
     }
     // A linearisation at z that a damping loop has asked for but nobody has needed yet.  levenberg_marquardt.m
     // (:189-194) and levenberg_marquardt_powell.m linearise at every ACCEPTED point before they test for
@@ -966,37 +977,36 @@ struct Core {
     void trace_only_pass(const double *zz) {
         stage(0);
         prep_cams(zz);
-        if (n_cm_chunks_all > 0) {
-            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15, MAXCOL>(tile_ncx, [&](auto NCX) {
-                launch<k_trace_cm<M, NCX>>(dim3((unsigned)n_cm_chunks_all), dim3(256), 0, d, zz, cams.p, cm_pt.p, cm_uv.p, pw ? cm_w.p : (const double *)nullptr,
+        if (part.n_cm_chunks_all > 0)
+            with_model([&](auto M) { with_value<6, 14, 15, MAXCOL>(tile_ncx, [&](auto NCX) {
+                launch<k_trace_cm<M, NCX>>(dim3((unsigned)part.n_cm_chunks_all), dim3(256), 0, d, zz, cams.p, cm_pt.p, cm_uv.p, pw ? cm_w.p : (const double *)nullptr,
                                            cm_chunk_cam.p, cm_chunk_start.p, partial.p);
             }); });
-        }
-        launch<k_trace_tail>(dim3(grid_zs), dim3(1024), 0, d, gpart.p, gctr.p + 6, (const double *)partial.p, n_cm_chunks_all, hpin, ++mb_seq);
+        launch<k_trace_tail>(dim3(grid_zs), dim3(1024), 0, d, gpart.p, gctr.p + CTR_TRACE_TAIL, (const double *)partial.p, part.n_cm_chunks_all, mailbox, ++mb_seq);
         mb_armed = true; lin_pending = true;
         sync();
-        pend_build = false;
-        lambda_lin = NAN; have_lin = false; s_valid = false;
+        pend_build = false; lambda_lin = NAN; have_lin = false; s_valid = false;
         ++n_trace_only;
+    }
+    // the whole linearisation on the stream: the build, the sum over the ranks, k_finish (also: trace(J'J) of the camera
+    // part and red_scal -> mailbox).  d.trace_only, where build() has set it, holds for the build's launches alone.
+    void linearise_enqueue(const double *zz, double lambda, int scale) {
+        try { build_enqueue(zz, lambda, scale); } catch (...) { d.trace_only = 0; throw; }
+        d.trace_only = 0;
+        if (mg_subtree) allreduce_vectors(); else allreduce_system();
+        finish_enqueue(zz, lambda, scale);
     }
     void build(const double *zz, double lambda, int scale, bool lazy = false, bool trace_only = false) {
         if (trace_only && !multi() && P.nranks == 1) { trace_only_pass(zz); return; }
         pend_build = false;
-        trace_only = trace_only && use_sig && ntiles > 0;
-        d.trace_only = trace_only ? 1 : 0;             // an argument of this launch (DevProblem travels by value)
-        try { build_enqueue(zz, lambda, scale); } catch (...) { d.trace_only = 0; throw; }
-        d.trace_only = 0;
-        if (mg_subtree) allreduce_vectors();
-        else allreduce_system();
-        finish_enqueue(zz, lambda, scale);           // also: trace(J'J) of the camera part and red_scal -> mailbox
+        trace_only = trace_only && route == TileRoute::sig;
+        d.trace_only = trace_only ? 1 : 0;             // an argument of the build's launches (DevProblem travels by value)
+        linearise_enqueue(zz, lambda, scale);
         if (mg_subtree && replicate_next && multi()) allreduce_matrix();   // (posterior covariance: the whole system on every rank)
-        cams_at_lin = true;                          // (zlin = zz: k_build_tail)
-        lin_pending = true;
+        cams_at_lin = true; lin_pending = true;      // (zlin = zz: k_build_tail)
         if (!lazy) sync();
-        lambda_lin = trace_only ? NAN : lambda;
-        scale_lin = scale;
-        have_lin = !trace_only;
-        s_valid = !trace_only;
+        lambda_lin = trace_only ? NAN : lambda; scale_lin = scale;
+        have_lin = s_valid = !trace_only;
         if (!trace_only) ++n_lin; else ++n_trace_only;
     }
     bool replicate_next = false;     // domain mode: the next build sums the whole matrix after k_finish (in-place factorisation)
@@ -1012,7 +1022,7 @@ struct Core {
         int *df_ctl = nullptr; unsigned long long *df_q = nullptr; int df_nq = 0;
         const bool ride = use_perm && !chol_in_place && !(mg_subtree && multi()) && dfchol.reset_args(df_ctl, df_q, df_nq);
         launch<k_finish>(dim3((unsigned)cdiv(P.NS, 256)), dim3(256), 0, d, zz, lambda, scale, S, g_c, g_red, diagU, jn2c.p, dscale.p,
-                gpart.p, gctr.p + 3, (const double *)red_scal, scal.p, hpin, mg_subtree && multi() ? (const uint8_t *)z_mine.p : (const uint8_t *)nullptr,
+                gpart.p, gctr.p + CTR_FINISH, (const double *)red_scal, scal.p, mailbox, mg_subtree && multi() ? (const uint8_t *)z_mine.p : (const uint8_t *)nullptr,
                 ride ? info.p : (int *)nullptr, ride ? df_ctl : (int *)nullptr, ride ? df_q : (unsigned long long *)nullptr, ride ? df_nq : 0);
         if (ride) dfchol.reset_done = true;
         if (scale)      // D S D on the envelope
@@ -1052,33 +1062,28 @@ struct Core {
         stage(2);
         mark(4);
         // the points of the signature chunks by k_backsub_sig (one wave per chunk), the other batches by
-        // k_backsub; partial: [nb batches][2] (the tiled batches' slots stay zero), giants, sig workgroups
-        const bool sig_bs = use_sig && P.sg_backsub_ok;
-        const int64_t b_first = sig_bs ? P.nb_tiled : 0;
-        const int64_t n_sig_wg = sig_bs ? cdiv(sg_nchunks, 4) : 0;
-        // (the slots of the tiled batches are not written then, and not summed: see k_sum_partials below)
-        if (n_sig_wg > 0) {
-            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14>(tile_ncx, [&](auto NCX) {
-                launch<k_backsub_sig<M, NCX>>(dim3((unsigned)n_sig_wg), dim3(256), 0, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p + 2 * (nb + ngiant), sg_chunk.p,
+        // k_backsub; partial (PartialLayout): [nb batches][2], giants, sig workgroups
+        // (the slots of the tiled batches are not written then, and not summed)
+        const int64_t b_first = part.bs_first_batch, n_sig_wg = part.bs_sig_wgs;
+        if (n_sig_wg > 0)
+            with_model([&](auto M) { with_value<6, 14>(tile_ncx, [&](auto NCX) {
+                launch<k_backsub_sig<M, NCX>>(dim3((unsigned)n_sig_wg), dim3(256), 0, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p + part.bs_sig, sg_chunk.p,
                                               (int)sg_nchunks, sg_gcam.p, sg_uv.p, pw ? sg_w.p : (const double *)nullptr);
             }); });
-        }
-        if (nb > b_first) {
-            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15, MAXCOL>(tile_ncx, [&](auto NCX) {
+        if (nb > b_first)
+            with_model([&](auto M) { with_value<6, 14, 15, MAXCOL>(tile_ncx, [&](auto NCX) {
                 launch<k_backsub<M, NCX>>(dim3((unsigned)(nb - b_first)), dim3(P.BT), lds_back, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p, (int)b_first);
             }); });
-        }
-        if (ngiant > 0) {
-            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
-                launch<k_backsub_giant<M, IO>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p + 2 * nb);
+        if (ngiant > 0)
+            with_model([&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
+                launch<k_backsub_giant<M, IO>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, zlin.p, cams.p, Vinv.p, gp.p, dz.p, partial.p + part.bs_giants);
             }); });
-        }
         mark(5);
         // one launch: the sums of the back-substitution kernels, the prior rows' share, g'p, p'p, the pivot
         // extremes of the reduced system; on one rank straight into the pinned mailbox
-        launch<k_prior_jv>(dim3(grid_zs), dim3(1024), 0, d, zlin.p, dz.p, g_c, gp.p, gpart.p, gctr.p + 4,
-                (const double *)(partial.p + 2 * b_first), nb - b_first + ngiant + n_sig_wg, (const double *)ldiag.p, pivmm.p,
-                (const int *)info.p, scal.p, multi() ? (double *)nullptr : hpin, ++mb_seq,
+        launch<k_prior_jv>(dim3(grid_zs), dim3(1024), 0, d, zlin.p, dz.p, g_c, gp.p, gpart.p, gctr.p + CTR_PRIOR_JV,
+                (const double *)(partial.p + part.bs_first), part.bs_count, (const double *)ldiag.p, pivmm.p,
+                (const int *)info.p, scal.p, multi() ? (double *)nullptr : mailbox, ++mb_seq,
                 mg_subtree && multi() ? (const uint8_t *)piv_have.p : (const uint8_t *)nullptr);
     }
     // solve at the current linearisation: p in dz.  Returns true if the
@@ -1099,32 +1104,30 @@ struct Core {
         if (!cams_at_lin) { prep_cams(zlin.p); cams_at_lin = true; }     // something else used the camera records since build()
         backsub_enqueue();
         int hinfo = 0;
-        unsigned long long hmm[4];
+        double mm[MB_PIVOTS_N];                      // (the pivot extremes are doubles, compared as their bit patterns on the device)
         // one all-reduce per solve: the 8 scalar sums (slot 7: a failed factorisation on any rank) and, behind
         // them, two {min,max} slots per rank with this rank's pivots of the point blocks and of the part of
         // the reduced system it factored (the extremes travel through the sum)
-        const int nsl = multi() ? 4 * P.nranks : 0;
-        std::vector<double> h((size_t)8 + nsl);
+        const int nsl = multi() ? SCAL_PER_RANK * P.nranks : 0;
+        std::vector<double> h((size_t)SCAL_SUMS + nsl);
         if (nsl) {
-            HIPCHK(hipMemcpyAsync(hpin + 40, pivmm.p, sizeof(hmm), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(hpin + 44, info.p, sizeof(hinfo), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemsetAsync(scal.p + 8, 0, (size_t)nsl * sizeof(double), stream));
-            HIPCHK(hipMemcpyAsync(scal.p + 8 + 4 * P.rank, pivmm.p, 4 * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            do_allreduce(scal.p, 8 + nsl);
-            read_scal(h.data(), 8 + nsl);
+            HIPCHK(hipMemcpyAsync(mailbox + MB_PIVOTS, pivmm.p, sizeof(mm), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(mailbox + MB_INFO, info.p, sizeof(hinfo), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemsetAsync(scal.p + SCAL_RANK0, 0, (size_t)nsl * sizeof(double), stream));
+            HIPCHK(hipMemcpyAsync(scal.p + SCAL_RANK0 + SCAL_PER_RANK * P.rank, pivmm.p, SCAL_PER_RANK * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            do_allreduce(scal.p, SCAL_SUMS + nsl);
+            read_scal(h.data(), SCAL_SUMS + nsl);
         } else {             // k_prior_jv left everything in the mailbox
             mb_armed = true;
             sync();
-            memcpy(h.data(), hpin, 8 * sizeof(double));
+            memcpy(h.data(), mailbox + MB_SCAL, SCAL_SUMS * sizeof(double));
         }
-        memcpy(hmm, hpin + 40, sizeof(hmm));
-        memcpy(&hinfo, hpin + 44, sizeof(hinfo));
-        JpJp = h[0] + h[4]; rJp = h[1] + h[5]; pp = h[6];
-        double mm[4];
-        memcpy(mm, hmm, sizeof(mm));
+        memcpy(mm, mailbox + MB_PIVOTS, sizeof(mm));
+        memcpy(&hinfo, mailbox + MB_INFO, sizeof(hinfo));
+        JpJp = h[SCAL_JPJP] + h[SCAL_JPJP_PRIOR]; rJp = h[SCAL_RJP] + h[SCAL_RJP_PRIOR]; pp = h[SCAL_PP];
         double pmin = std::min(mm[0], mm[2]), pmax = std::max(mm[1], mm[3]);
-        for (int r = 0; r < nsl / 2; ++r) { pmin = std::min(pmin, h[8 + 2 * r]); pmax = std::max(pmax, h[8 + 2 * r + 1]); }
-        const bool failed = hinfo != 0 || (nsl && h[7] > 0) || !std::isfinite(pp) || !std::isfinite(JpJp);
+        for (int r = 0; r < nsl / 2; ++r) { pmin = std::min(pmin, h[SCAL_RANK0 + 2 * r]); pmax = std::max(pmax, h[SCAL_RANK0 + 2 * r + 1]); }
+        const bool failed = hinfo != 0 || (nsl && h[SCAL_FAILED] > 0) || !std::isfinite(pp) || !std::isfinite(JpJp);
         // a failed factorisation that ran in place may have left non-finite values in tile parts outside the
         // column envelope (0 x NaN), which the envelope-only clearing of the next build would not reach
         if (failed && !(use_perm && !chol_in_place)) s_dense_dirty = true;
@@ -1196,7 +1199,7 @@ struct Core {
         if (hCOP) {
             dCOP.alloc((size_t)9 * P.np);
             HIPCHK(hipMemsetAsync(dCOP.p, 0, (size_t)9 * P.np * sizeof(double), stream));
-            with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
+            with_model([&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
                 if (nb > 0) launch<k_cov_points<M, IO>>(dim3((unsigned)nb), dim3(P.BT), lds_cov, d, z.p, cams.p, Vinv.p, SV, s02, dCOP.p, HatOut{});
                 if (ngiant > 0) launch<k_cov_giant<M, IO>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, z.p, cams.p, Vinv.p, SV, s02, dCOP.p, HatOut{});
             }); });
@@ -1234,7 +1237,7 @@ struct Core {
             gscr.alloc((size_t)(P.giant_start.back() - P.giant_start.front()) * 9);
             hat.gscr = gscr.p;
         }
-        with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
+        with_model([&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
             if (nb > 0) launch<k_cov_points<M, IO, true>>(dim3((unsigned)nb), dim3(P.BT), lds_cov, d, z.p, cams.p, Vinv.p, SV, 1.0, (double *)nullptr, hat);
             if (ngiant > 0) launch<k_cov_giant<M, IO, true>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, z.p, cams.p, Vinv.p, SV, 1.0, (double *)nullptr, hat);
         }); });
@@ -1278,7 +1281,6 @@ struct Core {
         std::vector<unsigned long long> img_host;
         EventTimer<1> timer;                             // last point_depths: reset of the scratch + the two kernels
     } dep;
-    static constexpr int DEPTH_SLOT = 52;                // mailbox slots 52..54: no other kernel writes them
     // The built-in chirality veto (dbat_hip_set_chirality): at every trial point a damping loop consults its veto at,
     // the number of observations with !(depth > chir_thr) at zt; a non-zero count rejects.  Two words cross to the host
     // (the count and the smallest depth, kept for dbat_hip_chirality_stats), the parameter vector never does.
@@ -1317,13 +1319,13 @@ struct Core {
         o_w_base.alloc(n2);
         if (P.uniform_w) {
             o_w.alloc(n2); cm_w.alloc(n2);
-            if (use_sig) { sg_w.alloc(n2); HIPCHK(hipMemsetAsync(sg_w.p, 0, n2 * sizeof(double), stream)); }   // slots outside the groups stay 0
+            if (route == TileRoute::sig) { sg_w.alloc(n2); HIPCHK(hipMemsetAsync(sg_w.p, 0, n2 * sizeof(double), stream)); }   // slots outside the groups stay 0
             if (nobs > 0) launch<k_robust_base>(dim3(robust_grid()), dim3(256), 0, nobs, (const int32_t *)o_cam.p, (const double *)cam_w.p, o_w_base.p);
         } else if (nobs > 0) {
             HIPCHK(hipMemcpyAsync(o_w_base.p, o_w.p, (size_t)2 * nobs * sizeof(double), hipMemcpyDeviceToDevice, stream));
         }
         cm_map.upload(cm_slots());
-        if (use_sig) {   // slot-major slot: group g, slot j, point i at obs0_g + j*m_g + i (plan.hpp, signature groups)
+        if (route == TileRoute::sig) {   // slot-major slot: group g, slot j, point i at obs0_g + j*m_g + i (plan.hpp, signature groups)
             std::vector<int32_t> sgm((size_t)nobs, -1);
             for (size_t q = 0; q < P.sg_chunk.size() / 8; ++q) {
                 const int32_t *ch = &P.sg_chunk[8 * q];
@@ -1340,7 +1342,7 @@ struct Core {
     void robust_apply_omega() {         // o_w, sg_w, cm_w from omega
         if (nobs > 0)
             launch<k_robust_apply<false>>(dim3(robust_grid()), dim3(256), 0, nobs, (const uint64_t *)nullptr, 1.0, 0, 1.0, omega.p, (const double *)o_w_base.p, o_w.p,
-                                          (const int32_t *)(use_sig ? sg_map.p : nullptr), sg_w.p, (const int32_t *)cm_map.p, cm_w.p);
+                                          (const int32_t *)(route == TileRoute::sig ? sg_map.p : nullptr), sg_w.p, (const int32_t *)cm_map.p, cm_w.p);
         s_valid = false;
     }
     void robust_set_ones() {
@@ -1352,12 +1354,12 @@ struct Core {
             HIPCHK(hipStreamSynchronize(stream));
             if (P.uniform_w) {
                 dev_free(o_w); dev_free(cm_w);
-                if (use_sig) dev_free(sg_w);
+                if (route == TileRoute::sig) dev_free(sg_w);
                 d.o_w = nullptr;
             } else {             // the plan's weights, as init() uploaded them
                 HIPCHK(hipMemcpy(o_w.p, P.o_w.data(), P.o_w.size() * sizeof(double), hipMemcpyHostToDevice));
                 HIPCHK(hipMemcpy(cm_w.p, P.cm_w.data(), P.cm_w.size() * sizeof(double), hipMemcpyHostToDevice));
-                if (use_sig) HIPCHK(hipMemcpy(sg_w.p, P.sg_w.data(), P.sg_w.size() * sizeof(double), hipMemcpyHostToDevice));
+                if (route == TileRoute::sig) HIPCHK(hipMemcpy(sg_w.p, P.sg_w.data(), P.sg_w.size() * sizeof(double), hipMemcpyHostToDevice));
             }
             dev_free(o_w_base); dev_free(omega); dev_free(sg_map); dev_free(cm_map);
             robust_on = false; pw = !P.uniform_w; s_valid = false;
@@ -1426,7 +1428,7 @@ struct Core {
         robust_promote();
         if (nobs > 0)
             launch<k_robust_apply<true>>(dim3(robust_grid()), dim3(256), 0, nobs, (const uint64_t *)rs_bits.p, scale, (int)ro.loss, ro.k, omega.p,
-                                         (const double *)o_w_base.p, o_w.p, (const int32_t *)(use_sig ? sg_map.p : nullptr), sg_w.p,
+                                         (const double *)o_w_base.p, o_w.p, (const int32_t *)(route == TileRoute::sig ? sg_map.p : nullptr), sg_w.p,
                                          (const int32_t *)cm_map.p, cm_w.p);
         s_valid = false;
     }
@@ -1444,19 +1446,19 @@ struct Core {
     // ||J v||^2 and r'Jv at the linearisation point, ||v||^2 over owned entries
     void jtimes(const double *v, double &JvJv, double &rJv, double &vv) {
         if (!cams_at_lin) { prep_cams(zlin.p); cams_at_lin = true; }
-        with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15, MAXCOL>(tile_ncx, [&](auto NCX) {
-            launch<k_jtimes<M, NCX>>(dim3(grid_obs), dim3(256), 0, d, zlin.p, cams.p, v, partial.p);
+        with_model([&](auto M) { with_value<6, 14, 15, MAXCOL>(tile_ncx, [&](auto NCX) {
+            launch<k_jtimes<M, NCX>>(dim3((unsigned)part.grid_obs), dim3(256), 0, d, zlin.p, cams.p, v, partial.p);
         }); });
-        launch<k_prior_jv>(dim3(grid_zs), dim3(1024), 0, d, zlin.p, v, g_c, gp.p, gpart.p, gctr.p + 4,
-                (const double *)partial.p, (int64_t)grid_obs, (const double *)nullptr, pivmm.p, (const int *)info.p, scal.p, (double *)nullptr, 0ull, (const uint8_t *)nullptr);
-        do_allreduce(scal.p, 8);
-        double h[8];
-        read_scal(h, 8);
-        JvJv = h[0] + h[4]; rJv = h[1] + h[5]; vv = h[6];
+        launch<k_prior_jv>(dim3(grid_zs), dim3(1024), 0, d, zlin.p, v, g_c, gp.p, gpart.p, gctr.p + CTR_PRIOR_JV,
+                (const double *)partial.p, part.grid_obs, (const double *)nullptr, pivmm.p, (const int *)info.p, scal.p, (double *)nullptr, 0ull, (const uint8_t *)nullptr);
+        do_allreduce(scal.p, SCAL_SUMS);
+        double h[SCAL_SUMS];
+        read_scal(h, SCAL_SUMS);
+        JvJv = h[SCAL_JPJP] + h[SCAL_JPJP_PRIOR]; rJv = h[SCAL_RJP] + h[SCAL_RJP_PRIOR]; vv = h[SCAL_PP];
     }
     double dot_owned(const double *a, const double *b) {
-        launch<k_dot>(dim3(grid_z), dim3(256), 0, P.NZ, z_mine.p, a, b, partial.p);
-        launch<k_sum_partials<1>>(dim3(1), dim3(1024), 0, partial.p, (int64_t)grid_z, scal.p, 0);
+        launch<k_dot>(dim3((unsigned)part.grid_z), dim3(256), 0, P.NZ, z_mine.p, a, b, partial.p);
+        launch<k_sum_partials<1>>(dim3(1), dim3(1024), 0, partial.p, part.grid_z, scal.p, 0);
         do_allreduce(scal.p, 1);
         double s;
         read_scal(&s, 1);
@@ -1473,7 +1475,7 @@ struct Core {
     }
     // Jacobian blocks of every observation at zz (the camera records in cams)
     void jac_blocks(const double *zz, double *a, double *b, double *cc) {
-        with_value<2, 3, 4, 5>(P.model, [&](auto M) { launch<k_jac_blocks<M>>(dim3((unsigned)cdiv(nobs, 256)), dim3(256), 0, d, zz, cams.p, a, b, cc); });
+        with_model([&](auto M) { launch<k_jac_blocks<M>>(dim3((unsigned)cdiv(nobs, 256)), dim3(256), 0, d, zz, cams.p, a, b, cc); });
     }
     void copy(double *dst, const double *src) { HIPCHK(hipMemcpyAsync(dst, src, P.NZ * 8, hipMemcpyDeviceToDevice, stream)); }
     void accept_trial() { std::swap(z.p, zt.p); }    // z <- the trial point: the buffers change roles (nothing keeps their addresses)
@@ -2087,7 +2089,7 @@ int dbat_hip_jacobian_sample(dbat_hip_handle *h, const double *x, int64_t n, con
     const int R = P.nIOrows;
     DevBuf<double> dr, a, b, cc;
     dr.alloc(2 * n); a.alloc(12 * n); b.alloc(6 * n); cc.alloc(2 * (int64_t)R * n);
-    with_value<2, 3, 4, 5>(P.model, [&](auto M) {
+    c.with_model([&](auto M) {
         c.launch<k_jac_sample<M>>(dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c.d, c.zt.p, c.cams.p, n, dpos.p, dr.p, a.p, b.p, cc.p);
     });
     HIPCHK(hipMemcpyAsync(res, dr.p, 2 * n * 8, hipMemcpyDeviceToHost, c.stream));
@@ -2253,7 +2255,7 @@ static void jtimes_rows(Core &c, const double *v_dev, double *Jv) {
     DevBuf<double> out;
     out.alloc(2 * std::max<int64_t>(P.no, 1));
     if (c.nobs > 0) {
-        with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<6, 14, 15, MAXCOL>(c.tile_ncx, [&](auto NCX) {
+        c.with_model([&](auto M) { with_value<6, 14, 15, MAXCOL>(c.tile_ncx, [&](auto NCX) {
             c.launch<k_jtimes_vec<M, NCX>>(dim3((unsigned)cdiv(c.nobs, 256)), dim3(256), 0, c.d, c.zlin.p, c.cams.p, v_dev, out.p);
         }); });
     }
@@ -2569,14 +2571,12 @@ int dbat_hip_bench_step(dbat_hip_handle *h, double lambda, int32_t scale_columns
     DeviceGuard dev_guard(c.device);
     c.timing = true;
     HIPCHK(hipEventRecord(c.ev[0], c.stream));
-    c.build_enqueue(c.z.p, lambda, scale_columns);
-    if (c.mg_subtree) c.allreduce_vectors(); else c.allreduce_system();
-    c.finish_enqueue(c.z.p, lambda, scale_columns);
+    c.linearise_enqueue(c.z.p, lambda, scale_columns);
     HIPCHK(hipEventRecord(c.ev[1], c.stream));
     c.factor_solve_enqueue();
     HIPCHK(hipEventRecord(c.ev[2], c.stream));
     c.backsub_enqueue();
-    c.do_allreduce(c.scal.p, 8);
+    c.do_allreduce(c.scal.p, SCAL_SUMS);
     HIPCHK(hipEventRecord(c.ev[3], c.stream));
     (void)c.eval_f_step(c.z.p, 1.0, c.dz.p, c.zt.p);              // trial-point residual, syncs
     HIPCHK(hipEventRecord(c.ev[4], c.stream));

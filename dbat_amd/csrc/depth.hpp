@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "model.hpp"
+#include "step_layout.hpp"
 
 namespace dbat {
 
@@ -123,8 +124,8 @@ __global__ __launch_bounds__(256) void k_depth_cm(const double *__restrict__ z, 
 
 __device__ __forceinline__ void mailbox_done(double *mailbox, unsigned long long seq);      // (kernels.hpp)
 
-// mailbox[slot .. slot + 2] = {count (as an integer's bit pattern), smallest depth (NaN: none), its smallest IP column
-// (bit pattern; -1: none, and where FULL is off)}, then the host's ticket
+// mailbox[slot ..] (slot: MB_DEPTH, laid out as MB_DEPTH_BEHIND / _MIN / _ARGMIN) = {count (as an integer's bit pattern),
+// smallest depth (NaN: none), its smallest IP column (bit pattern; -1: none, and where FULL is off)}, then the host's ticket
 template <bool FULL>
 __global__ __launch_bounds__(256) void k_depth_finish(int64_t nchunks, const unsigned long long *__restrict__ red,
                                                       const unsigned long long *__restrict__ chunk_key, const long long *__restrict__ chunk_col,
@@ -143,9 +144,9 @@ __global__ __launch_bounds__(256) void k_depth_finish(int64_t nchunks, const uns
             for (int w = 1; w < 4; ++w) col = s_col[w] < col ? s_col[w] : col;
     }
     if (threadIdx.x != 0) return;
-    mailbox[slot] = __longlong_as_double((long long)red[0]);
-    mailbox[slot + 1] = depth_from_key(gmin);
-    mailbox[slot + 2] = __longlong_as_double(col == DEPTH_NO_COL ? -1ll : col);
+    mailbox[slot + (MB_DEPTH_BEHIND - MB_DEPTH)] = __longlong_as_double((long long)red[0]);
+    mailbox[slot + (MB_DEPTH_MIN - MB_DEPTH)] = depth_from_key(gmin);
+    mailbox[slot + (MB_DEPTH_ARGMIN - MB_DEPTH)] = __longlong_as_double(col == DEPTH_NO_COL ? -1ll : col);
     mailbox_done(mailbox, seq);
 }
 

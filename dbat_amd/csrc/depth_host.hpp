@@ -24,7 +24,7 @@ static void depth_plan(Core &c) {
 }
 
 // the depth kernels at zz with the camera records cams_f; FULL: depths, per-image minima and the argmin as well.
-// Results: the mailbox (hpin[DEPTH_SLOT ..]) once the stream has run (ticket mb_seq).
+// Results: the mailbox (MB_DEPTH .., step_layout.hpp) once the stream has run (ticket mb_seq).
 template <bool FULL>
 static void depth_enqueue(Core &c, const double *zz, double thr, bool want_depth) {
     Core::DepthPlan &dep = c.dep;
@@ -37,7 +37,7 @@ static void depth_enqueue(Core &c, const double *zz, double thr, bool want_depth
                                    (const int32_t *)c.cm_chunk_cam.p, (const int64_t *)c.cm_chunk_start.p, (const int64_t *)dep.cm_col.p, thr,
                                    want_depth ? dep.depth.p : (double *)nullptr, dep.red.p, img, ckey, dep.chunk_col.p);
     c.launch<k_depth_finish<FULL>>(dim3(1), dim3(256), 0, c.n_cm_chunks_all, (const unsigned long long *)dep.red.p, (const unsigned long long *)ckey,
-                                   (const long long *)dep.chunk_col.p, c.hpin, Core::DEPTH_SLOT, ++c.mb_seq);
+                                   (const long long *)dep.chunk_col.p, c.mailbox, MB_DEPTH, ++c.mb_seq);
 }
 static int64_t mailbox_int(const double *slot) { int64_t v; memcpy(&v, slot, sizeof v); return v; }
 
@@ -54,7 +54,7 @@ static void point_depths(Core &c, double thr, double *hdepth, double *himg, int6
         HIPCHK(hipMemcpyAsync(dep.img_host.data(), dep.red.p + 2, (size_t)P.nc * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
     c.sync();                                            // (not armed: the copies behind the ticket are waited for too)
     if (himg) for (int i = 0; i < P.nc; ++i) himg[i] = depth_from_key(dep.img_host[i]);
-    n_behind = mailbox_int(c.hpin + Core::DEPTH_SLOT); min_depth = c.hpin[Core::DEPTH_SLOT + 1]; argmin = mailbox_int(c.hpin + Core::DEPTH_SLOT + 2);
+    n_behind = mailbox_int(c.mailbox + MB_DEPTH_BEHIND); min_depth = c.mailbox[MB_DEPTH_MIN]; argmin = mailbox_int(c.mailbox + MB_DEPTH_ARGMIN);
     dep.timer.read();
 }
 
@@ -63,10 +63,10 @@ bool Core::chirality_veto() {                            // right after eval_f_s
     depth_enqueue<false>(*this, zt.p, chir_thr, false);
     mb_armed = true;
     sync();
-    const int64_t nb = mailbox_int(hpin + DEPTH_SLOT);
+    const int64_t nb = mailbox_int(mailbox + MB_DEPTH_BEHIND);
     ++veto_tested;
     if (nb == 0) return false;
-    ++veto_rejected; veto_n_behind = nb; veto_min_depth = hpin[DEPTH_SLOT + 1];
+    ++veto_rejected; veto_n_behind = nb; veto_min_depth = mailbox[MB_DEPTH_MIN];
     return true;
 }
 }  // namespace dbat
@@ -121,7 +121,7 @@ int dbat_hip_debug_chirality_pass_ms(dbat_hip_handle *h, const double *x, int32_
     for (int i = 0; i < reps; ++i) depth_enqueue<false>(c, c.zt.p, c.chir_thr, false);
     timer.lap(c.stream);
     c.sync();
-    ms[0] = (float)timer.read() / reps; ms[1] = (double)mailbox_int(c.hpin + Core::DEPTH_SLOT);
+    ms[0] = (float)timer.read() / reps; ms[1] = (double)mailbox_int(c.mailbox + MB_DEPTH_BEHIND);
     return DBAT_HIP_OK;
     API_CATCH
 }

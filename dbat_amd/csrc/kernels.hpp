@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "model.hpp"
+#include "step_layout.hpp"
 
 namespace dbat {
 
@@ -376,16 +377,16 @@ __global__ __launch_bounds__(256) void k_residual_cm(DevProblem d, const double 
     if (threadIdx.x == 0) {
         out[0] = tot[0];
         __hip_atomic_store(tail_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (mailbox) { mailbox[0] = tot[0]; mailbox_done(mailbox, seq); }
+        if (mailbox) { mailbox[MB_OBJECTIVE] = tot[0]; mailbox_done(mailbox, seq); }
     }
 }
 
 // The last word a kernel says to the host: after its results are in the pinned mailbox it stores the
-// ticket of the host's current wait in slot 63 (system-scope release).  The host spins on that slot
+// ticket of the host's current wait in slot MB_TICKET (system-scope release).  The host spins on that slot
 // instead of sleeping in hipStreamSynchronize -- kernels of a stream finish in order, so the ticket
 // of the last one means everything before it is done.
 __device__ __forceinline__ void mailbox_done(double *mailbox, unsigned long long seq) {
-    __atomic_store_n(reinterpret_cast<unsigned long long *>(mailbox) + 63, seq, __ATOMIC_RELEASE);
+    __atomic_store_n(reinterpret_cast<unsigned long long *>(mailbox) + MB_TICKET, seq, __ATOMIC_RELEASE);
 }
 
 // prior-observation rows (prior_obs.m:26-43): sum over owned z of w*(z-prior)^2, plus the n_res partial
@@ -407,7 +408,7 @@ __global__ __launch_bounds__(1024) void k_prior_sq(DevProblem d, const double *_
         }
     if (grid_sum<1, 1>(acc, sh, partial, ctr, res_partial, n_res) && threadIdx.x == 0) {
         out[0] = acc[0];
-        if (mailbox) { mailbox[0] = acc[0]; mailbox_done(mailbox, seq); }
+        if (mailbox) { mailbox[MB_OBJECTIVE] = acc[0]; mailbox_done(mailbox, seq); }
     }
 }
 
@@ -461,7 +462,7 @@ __global__ __launch_bounds__(1024) void k_trace_tail(DevProblem d, double *__res
         if (w > 0 && d.z_est[i] && d.z_mine[i]) acc[0] += w;
     }
     if (grid_sum<1, 1>(acc, sh, partial, ctr, obs_partial, n_obs_partial) && threadIdx.x == 0) {
-        mailbox[32] = 0.0; mailbox[33] = acc[0]; mailbox[34] = 0.0;       // (f of the linearisation point: not computed here)
+        mailbox[MB_LIN_RR] = 0.0; mailbox[MB_LIN_TRACE_PT] = acc[0]; mailbox[MB_LIN_TRACE_CAM] = 0.0;       // (f of the linearisation point: not computed here)
         mailbox_done(mailbox, seq);
     }
 }
@@ -2849,7 +2850,7 @@ __global__ void k_finish(DevProblem d, const double *__restrict__ z, double lamb
     }
     if (grid_sum<1>(acc, sh, partial, ctr) && threadIdx.x == 0) {
         out[0] = acc[0];
-        if (mailbox) { mailbox[34] = acc[0]; mailbox[32] = red_scal[0]; mailbox[33] = red_scal[1]; }   // slots no other kernel writes
+        if (mailbox) { mailbox[MB_LIN_TRACE_CAM] = acc[0]; mailbox[MB_LIN_RR] = red_scal[0]; mailbox[MB_LIN_TRACE_PT] = red_scal[1]; }   // slots no other kernel writes
     }
 }
 
@@ -3077,8 +3078,8 @@ __global__ __launch_bounds__(256) void k_jtimes_vec(DevProblem d, const double *
 // The tail of a solve in one launch: the sums above -> out[4..6]; the back-substitution kernels'
 // (or k_jtimes') nbs partial sum pairs over the image rows -> out[0], out[1]; the extremes
 // of the Cholesky pivots ldiag of the reduced system (estimated entries) -> pivmm[2..3]; and,
-// with a mailbox, everything the host reads after a solve: out[0..7] -> mailbox[0..7],
-// pivmm[0..3] -> mailbox[40..43], *info -> mailbox[44].
+// with a mailbox, everything the host reads after a solve (step_layout.hpp): the sums out[SCAL_*] -> mailbox[MB_JPJP ..
+// MB_PP], pivmm[0..3] -> mailbox[MB_PIVOTS ..], *info -> mailbox[MB_INFO].
 __global__ __launch_bounds__(1024) void k_prior_jv(DevProblem d, const double *__restrict__ z,
                                                   const double *__restrict__ v, const double *__restrict__ g_c,
                                                   const double *__restrict__ gp, double *__restrict__ partial,
@@ -3115,17 +3116,17 @@ __global__ __launch_bounds__(1024) void k_prior_jv(DevProblem d, const double *_
         __builtin_amdgcn_s_waitcnt(0);               // performed before this block's ticket
     }
     if (grid_sum<5, 2, 3>(acc, sh, partial, ctr, bs_partial, nbs, 2) && threadIdx.x == 0) {
-        out[0] = acc[3]; out[1] = acc[4]; out[4] = acc[0]; out[5] = acc[1]; out[6] = acc[2];
+        out[SCAL_JPJP] = acc[3]; out[SCAL_RJP] = acc[4]; out[SCAL_JPJP_PRIOR] = acc[0]; out[SCAL_RJP_PRIOR] = acc[1]; out[SCAL_PP] = acc[2];
         // a failed factorisation on ANY rank must be seen by all of them (out is summed over the ranks)
-        out[7] = info && __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ? 1.0 : 0.0;
+        out[SCAL_FAILED] = info && __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ? 1.0 : 0.0;
         out[2] = 0.0; out[3] = 0.0;
         if (mailbox) {
-            mailbox[0] = acc[3]; mailbox[1] = acc[4]; mailbox[4] = acc[0]; mailbox[5] = acc[1]; mailbox[6] = acc[2];
-            for (int q = 0; q < 4; ++q)
-                mailbox[40 + q] = __longlong_as_double((long long)__hip_atomic_load(pivmm + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            mailbox[MB_JPJP] = acc[3]; mailbox[MB_RJP] = acc[4]; mailbox[MB_JPJP_PRIOR] = acc[0]; mailbox[MB_RJP_PRIOR] = acc[1]; mailbox[MB_PP] = acc[2];
+            for (int q = 0; q < MB_PIVOTS_N; ++q)
+                mailbox[MB_PIVOTS + q] = __longlong_as_double((long long)__hip_atomic_load(pivmm + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
             const int hi = __hip_atomic_load(info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             long long w = hi;
-            mailbox[44] = __longlong_as_double(w);
+            mailbox[MB_INFO] = __longlong_as_double(w);
             mailbox_done(mailbox, seq);
         }
     }

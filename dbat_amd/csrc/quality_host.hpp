@@ -82,7 +82,7 @@ static void residual_stats(Core &c, const PointIndex &ix, QualPlan &qual, int64_
     c.prep_cams(zz, c.cams_f.p);
     qual.res_timer.start(c.stream);
     if (c.nobs > 0)
-        with_value<2, 3, 4, 5>(P.model, [&](auto M) { with_value<false, true>(c.uv_pre, [&](auto PRE) {
+        c.with_model([&](auto M) { with_value<false, true>(c.uv_pre, [&](auto PRE) {
             c.launch<k_residual<M, PRE>>(dim3(c.grid_obs), dim3(256), 0, c.d, zz, c.cams_f.p, c.rpart.p, (double *)nullptr, qual.r.p);
         }); });
     if (nc > 0)

@@ -818,11 +818,11 @@ __global__ __launch_bounds__(64 * sig_waves(RB, (NCX > 6))) void k_build_sig(Dev
         ios = DBAT_SIG_ONLY_IOS;     // (register experiments: one instantiation per kernel)
 #endif
         if (NCX > 6 && ios == 1)
-            build_sig_tile<MODEL, RB, NCX, (NCX > 6 ? 1 : 0), PW>(d, tile, (int)ti, z, cams, lambda, scale, S, g_red, Vinv, gp, jn2p, partial, pivmm, sg_chunk, sg_tile_chunk0, sg_lc, sg_uv, sg_w, tile_ctr + 2, sy, sh);
+            build_sig_tile<MODEL, RB, NCX, (NCX > 6 ? 1 : 0), PW>(d, tile, (int)ti, z, cams, lambda, scale, S, g_red, Vinv, gp, jn2p, partial, pivmm, sg_chunk, sg_tile_chunk0, sg_lc, sg_uv, sg_w, tile_ctr + (CTR_SIG_TIMEOUTS - CTR_SIG_TICKET), sy, sh);
         else if (NCX > 6 && ios == 2)
-            build_sig_tile<MODEL, RB, NCX, (NCX > 6 ? 2 : 0), PW>(d, tile, (int)ti, z, cams, lambda, scale, S, g_red, Vinv, gp, jn2p, partial, pivmm, sg_chunk, sg_tile_chunk0, sg_lc, sg_uv, sg_w, tile_ctr + 2, sy, sh);
+            build_sig_tile<MODEL, RB, NCX, (NCX > 6 ? 2 : 0), PW>(d, tile, (int)ti, z, cams, lambda, scale, S, g_red, Vinv, gp, jn2p, partial, pivmm, sg_chunk, sg_tile_chunk0, sg_lc, sg_uv, sg_w, tile_ctr + (CTR_SIG_TIMEOUTS - CTR_SIG_TICKET), sy, sh);
         else
-            build_sig_tile<MODEL, RB, NCX, 0, PW>(d, tile, (int)ti, z, cams, lambda, scale, S, g_red, Vinv, gp, jn2p, partial, pivmm, sg_chunk, sg_tile_chunk0, sg_lc, sg_uv, sg_w, tile_ctr + 2, sy, sh);
+            build_sig_tile<MODEL, RB, NCX, 0, PW>(d, tile, (int)ti, z, cams, lambda, scale, S, g_red, Vinv, gp, jn2p, partial, pivmm, sg_chunk, sg_tile_chunk0, sg_lc, sg_uv, sg_w, tile_ctr + (CTR_SIG_TIMEOUTS - CTR_SIG_TICKET), sy, sh);
         __syncthreads();                             // the tile's LDS is free again (and s_ticket may be redrawn)
     }
 }

@@ -1810,3 +1810,60 @@ def test_signature_group_kernel_five_row_blocks(hip, rays, selfcal, monkeypatch)
     res, ok, iters, s0, E = bundle(s, 'gna')
     ro, oko, ito, s0o, Eo = o.bundle(s, 'gna')
     assert ok and oko and iters == ito and relerr(E.x, Eo.x) < TOL_X
+
+
+def _same_bits(a, b):
+    """Equal bit for bit (NaN included), through tuples and dicts."""
+    if isinstance(a, (tuple, list)):
+        return isinstance(b, (tuple, list)) and len(a) == len(b) and all(_same_bits(u, v) for u, v in zip(a, b))
+    if isinstance(a, dict):
+        return isinstance(b, dict) and sorted(a) == sorted(b) and all(_same_bits(a[k], b[k]) for k in a)
+    if a is None or b is None:
+        return a is b
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('variant', ['plain', 'selfcal'])
+def test_mailbox_users_share_one_handle(hip, variant):
+    """Every call that reports through the pinned mailbox (csrc/step_layout.hpp), one after the other on ONE handle:
+    objective value, a Levenberg-Marquardt solve whose first pass is the trace-only one (the linearisation sums), the
+    depth triple, the objective again, linearise + solve, the veto's statistics.  No call sees what another left in its
+    slots: each result equals, bit for bit, the same call on a fresh handle that did only that call (for the last two,
+    after the same solve).  Deterministic mode, chirality veto on."""
+    s, _ = synth_struct('tiny', variant)
+    opt = hip.default_options('lm')
+    opt.store_trace = 1
+    assert opt.lambda0 < 0 and opt.lambda_min < 0
+
+    def fresh():
+        h = hip.Handle(s)
+        h.set_deterministic(True)
+        h.set_chirality(True, 0.0)
+        return h
+
+    def solve(h, x0):
+        x, res, rr, damp, aux, T = h.solve(x0, opt)
+        assert res.n_trace_only == 1
+        return x, (res.code, res.iters, res.n_res, res.n_damp, res.n_trace, res.sigma0), rr, damp, T
+
+    h = fresh()
+    try:
+        x0 = h.serialize()
+        got = [h.residual(x0)]
+        got.append(solve(h, x0))
+        x = got[1][0]
+        got += [h.point_depths(x), h.residual(x0), h.linearize_solve(x0), h.chirality_stats()]
+    finally:
+        h.close()
+    alone = [lambda g: g.residual(x0), lambda g: solve(g, x0), lambda g: g.point_depths(x), lambda g: g.residual(x0),
+             lambda g: (solve(g, x0), g.linearize_solve(x0))[1], lambda g: (solve(g, x0), g.chirality_stats())[1]]
+    for i, call in enumerate(alone):
+        g = fresh()
+        try:
+            want = call(g)
+        finally:
+            g.close()
+        assert _same_bits(got[i], want), 'step %d' % (i + 1)
+    assert got[5][0] > 0                            # the veto was consulted during the solve
