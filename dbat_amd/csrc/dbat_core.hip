@@ -21,6 +21,7 @@
 #include "../../include/dbat_hip.h"
 #include "chol_df.hpp"
 #include "kernels.hpp"
+#include "cov.hpp"
 #include "sig.hpp"
 #include "heavy.hpp"
 #include "plan.hpp"
@@ -127,30 +128,42 @@ static inline void cpu_relax() {
 }
 
 struct Core {
+    // ======== what a handle holds: every data member, by section; the methods follow ========
     Plan P;
     DevProblem d{};
     hipStream_t stream = nullptr;
     int device = 0;
     int n_cu = 256;                  // compute units: launch size of the persistent tile kernel
     rocblas_handle blas = nullptr;
-    // pinned host mailbox for the scalar read-backs of the damping loops (a copy to pageable memory is
-    // staged and costs a blit kernel of ~18 us each, seven per LM step): MB_SIZE doubles, the slots MB_* of
-    // step_layout.hpp (DESIGN.md, "Step protocol": who writes and who reads each of them)
-    double *mailbox = nullptr;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t kev[13] = {};     // per-kernel brackets, recorded only while timing is on ([8], [9]: the all-reduce of the top tiles; [10 .. 12]: the kernels of the heavy / giant points)
     bool timing = false;
-    // static problem data
+    // kernels with more than 64 KiB of dynamic LDS must opt in on the device: the ones this handle has opted in, and
+    // at what size (a handle's launches run on its one device; a handle opts in at most 5 kernels)
+    struct { const void *kernel; size_t bytes; } lds_opt_in[8] = {};
+    int n_lds_opt_in = 0;
+
+    // ---- static problem data
     DevBuf<int32_t> cam_ncol, cam_col, cam_iorow, io_src, o_cam, o_pt;
     DevBuf<uint32_t> cam_eo_est, o_seg;
     DevBuf<double> io_fixed, px, cam_w, z_prw, z_prv, o_uv, o_w;
+    bool pw = false;                    // the kernels read per-observation weights (o_w, sg_w, cm_w): obs_weights()
+    DevBuf<double> o_rhs;               // fixed IO: the corrected image coordinates (k_uv_to_rhs), what d.o_uv points at
+    bool uv_pre = false;
+    DevBuf<uint8_t> z_est, z_mine, o_lc, o_pidx;
+    DevBuf<int64_t> o_row, batch_start, x2z, giant_start, cm_chunk_start;
+    DevBuf<int32_t> cm_pt, cm_chunk_cam, tile_order;
+    DevBuf<double> cm_uv, cm_w;
+    int64_t n_cm_chunks = 0, n_cm_chunks_all = 0;
+    int64_t nb = 0, nobs = 0;
+    int grid_obs = 1, grid_z = 1, grid_zs = 1;       // grid_zs: blocks of 1024 threads of the kernels that end in a grid sum
+    size_t lds_build = 0, lds_back = 0, lds_cov = 0;
     // deterministic mode (dbat_hip_set_deterministic): ticket counters and the turn of every tile / chunk at them
     bool deterministic = false;
     DevBuf<double> det_cam_part, det_io_part, det_rr, det_u;      // kernels.hpp DevProblem::deterministic
     DevBuf<int32_t> det_cam_chunks;
-    DevBuf<double> o_rhs;               // fixed IO: the corrected image coordinates (k_uv_to_rhs), what d.o_uv points at
-    bool uv_pre = false;
-    DevBuf<uint8_t> z_est, z_mine, o_lc, o_pidx;
+
+    // ---- route and tiles
     DevBuf<int32_t> tile_batch, tile_cam_start, tile_cams, tile_io_start, tile_iocols;
     DevBuf<uint8_t> tile_io_simple;
     DevBuf<uint8_t> tile_cam_io;
@@ -166,33 +179,69 @@ struct Core {
     // sig_rb row blocks; the sg_* copies exist on this route alone), k_build_tile3 (fixed IO), k_build_tile2
     // (self-calibration), or none (nothing tiled)
     enum class TileRoute { none, sig, tile3, tile2 } route = TileRoute::none;
-    template <class F> void with_model(F &&f) { with_value<2, 3, 4, 5>(P.model, f); }     // f(integral_constant): the lens model of the plan
-    DevBuf<int64_t> o_row, batch_start, x2z, giant_start, cm_chunk_start;
-    DevBuf<int32_t> cm_pt, cm_chunk_cam, tile_order;
-    DevBuf<double> cm_uv, cm_w;
-    int64_t n_cm_chunks = 0, n_cm_chunks_all = 0;
+
+    // ---- heavy / giant points on the matrix cores (heavy.hpp; Plan::hv_*)
     DevBuf<double> giant_W;
     int64_t ngiant = 0;
-    // heavy / giant points on the matrix cores (heavy.hpp; Plan::hv_*)
     bool use_heavy = false;
     HeavyDev hv{};
     DevBuf<int32_t> hv_obs_dst, hv_pt_io0, hv_io_dst, hv_io_pt, hv_pt_y, hv_grp_nb, hv_grp_row, hv_task, hv_ops;
     DevBuf<uint8_t> hv_obs_ld, hv_obs_ioloc, hv_io_ld;
     DevBuf<double> hv_Z;
     int giant_threads = 256;            // DBAT_HIP_GIANT_THREADS (64/128/256): tests force several chunks per point
-    // state
+
+    // ---- linearisation state
     DevBuf<CamRec> cams, cams_f;                     // camera records at the linearisation point / at the last objective evaluation
     bool cams_at_lin = false;                        // cams holds the records of zlin
     // experiment switches, read once at set-up (never in the per-iteration path)
-
     const char *env_df_trace = nullptr;
-    DevBuf<unsigned> gctr;                           // tickets of the in-kernel grid sums (zero between launches)
-    DevBuf<double> gpart, rpart;                     // their per-block partial sums; sink of k_residual's (unused) sums
     DevBuf<double> z, zt, dz, zlin, vtmp, vtmp2, xbuf;  // NZ each (xbuf: n)
     DevBuf<double> red;      // [S | g_red | g_c | diagU | scal(8)]
     // Vinv: six doubles per object point -- since round 3 the FACTOR R of the point block's inverse (V^-1 = R R',
     // kernels.hpp point_block_factor), not the inverse; gp: B'r per point; jn2p: squared column norms of the point columns
-    DevBuf<double> jn2c, dscale, rhs, Vinv, gp, jn2p, partial, scal;
+    DevBuf<double> jn2c, dscale, rhs, Vinv, gp, jn2p;
+    DevBuf<int> info;
+    DevBuf<double> linv, ldiag;
+    DataflowChol dfchol;                // persistent task-graph Cholesky, cameras in nested-dissection order (chol_df.hpp)
+    DataflowChol dfchol_ip;             // the same in place, natural order (posterior covariance: L must end up in S)
+    bool use_perm = true;
+    bool chol_in_place = false;         // next factorisation must leave L in S
+    int64_t ldS = 0;
+    CholEnvelope env;
+    DevBuf<unsigned long long> pivmm;   // [0..1] point pivots min/max, [2..3] reduced-system pivots
+    double *S = nullptr, *g_red = nullptr, *g_c = nullptr, *diagU = nullptr, *red_scal = nullptr;
+    int64_t red_count = 0;
+    double f_lin = 0, trace_jtj = 0, lambda_lin = 0;
+    int scale_lin = 0;
+    bool have_lin = false;
+    bool s_valid = false;      // S holds an unfactorised reduced system
+    bool s_dense_dirty = true; // S may hold non-zeros outside its envelope (fresh allocation, dense inverse)
+    // A linearisation at z that a damping loop has asked for but nobody has needed yet.  levenberg_marquardt.m
+    // (:189-194) and levenberg_marquardt_powell.m linearise at every ACCEPTED point before they test for
+    // termination; after the last accepted step that Jacobian is only returned (final.weighted.J), never
+    // used for a step.  Here it is built when the next solve -- or a caller who wants the gradient, the
+    // column norms or J v -- asks for it, and not at all otherwise: one build kernel chain less per solve
+    // (C3: 6 -> 5 linearisations for 4 LM iterations).  The iterates are the same, bit for bit.
+    bool pend_build = false;
+    double pend_lambda = 0;
+    int pend_scale = 0;
+    // the last solve(): near_singular mimics MATLAB's 'nearlySingularMatrix' warning (see solve())
+    bool near_singular = false;
+    const bool pivot_stats = env_on("DBAT_HIP_PIVOT_STATS");
+    double rcond_est = 0.0;      // (min pivot / max pivot)^2 of the last solve; 0 after a failed factorisation
+    int chol_info = 0;           // k_chol_df's info of the last solve: > 0 first non-positive pivot, -1 dataflow abort
+    double piv_last[4] = {0, 0, 0, 0};   // {min, max} pivot of the point blocks, {min, max} of the reduced system
+    // counters
+    int n_res_evals = 0, n_lin = 0, n_solves = 0, n_trace_only = 0;
+
+    // ---- step protocol
+    // pinned host mailbox for the scalar read-backs of the damping loops (a copy to pageable memory is
+    // staged and costs a blit kernel of ~18 us each, seven per LM step): MB_SIZE doubles, the slots MB_* of
+    // step_layout.hpp (DESIGN.md, "Step protocol": who writes and who reads each of them)
+    double *mailbox = nullptr;
+    DevBuf<unsigned> gctr;                           // tickets of the in-kernel grid sums (zero between launches)
+    DevBuf<double> gpart, rpart;                     // their per-block partial sums; sink of k_residual's (unused) sums
+    DevBuf<double> partial, scal;
     // Who writes where in `partial`, the per-workgroup sums that the tail kernels add up ("Step protocol"):
     // layout_partial() fills it in init(), nothing else computes an offset into the buffer.
     struct PartialLayout {
@@ -207,39 +256,65 @@ struct Core {
         int64_t doubles = 0;            // the allocation; end(): one past the last double that any user touches
         int64_t end() const { return std::max({build.total, build_det_lists.total, bs_sig + 2 * bs_sig_wgs, n_cm_chunks_all, 2 * grid_obs, grid_z}); }
     } part;
-    DevBuf<int> info;
-    DevBuf<double> linv, ldiag;
-    DataflowChol dfchol;                // persistent task-graph Cholesky, cameras in nested-dissection order (chol_df.hpp)
-    DataflowChol dfchol_ip;             // the same in place, natural order (posterior covariance: L must end up in S)
-    bool use_perm = true;
+    bool lin_pending = false;                        // k_finish's scalars are in the mailbox (or on their way), not read yet
+    bool det_timeout_pending = false;                // ... and the timeout count of the deterministic signature kernel
+    unsigned long long mb_seq = 0;                   // ticket of the last kernel that reports through mailbox slot 63
+    bool mb_armed = false;                           // ... and such a kernel is the last one enqueued
+
+    // ---- multi-rank
     bool mg_subtree = false;            // several ranks, domain sharding (nd.hpp): local factorisation + all-reduce of the top tiles
     DevBuf<uint8_t> piv_have;           // ... pivots of the reduced system that this rank computes
-    bool chol_in_place = false;         // next factorisation must leave L in S
-    int64_t ldS = 0;
-    CholEnvelope env;
-    DevBuf<unsigned long long> pivmm;   // [0..1] point pivots min/max, [2..3] reduced-system pivots
-    double *S = nullptr, *g_red = nullptr, *g_c = nullptr, *diagU = nullptr, *red_scal = nullptr;
-    int64_t red_count = 0;
     // multi-GPU: envelope of S + the vectors, contiguous (what the all-reduce carries)
     DevBuf<double> pk;
     DevBuf<int> col_bend;
     DevBuf<int64_t> col_off;
     int64_t pk_s_count = 0;
     int env_tail0 = 0;
-    int64_t nb = 0, nobs = 0;
-    int grid_obs = 1, grid_z = 1, grid_zs = 1;       // grid_zs: blocks of 1024 threads of the kernels that end in a grid sum
-    size_t lds_build = 0, lds_back = 0, lds_cov = 0;
     // multi-GPU: the RCCL communicator of this handle's rank (dbat_hip_comm_init), or the
     // caller's all-reduce callback (gloo / host tests)
     ncclComm_t nccl = nullptr;
     dbat_hip_allreduce_fn allreduce = nullptr;
     void *allreduce_user = nullptr;
     DevBuf<double> zgather;             // [NZ] owned entries of a z-vector, summed over the ranks
+    bool replicate_next = false;     // domain mode: the next build sums the whole matrix after k_finish (in-place factorisation)
+
+    // ---- The parameter trace of a damping loop (bundle.m's T: x of every iteration), kept ON THE DEVICE while the loop
+    // runs -- one gather kernel per column, no copy and no wait -- and brought down once at the end.  (Round 5 fetched
+    // every column when it was made: a 24 MB copy into pageable memory and a synchronisation per iteration at C3, then a
+    // second copy into the caller's array.)  Columns a loop never wrote come back as NaN.
+    DevBuf<double> trace_dev;
+    int trace_cap = 0, trace_n = 0;
+    std::vector<uint8_t> trace_have;
+
+    // ---- stage timers of a solve (dbat_hip_result.stage_s): an event where a stage is enqueued; the stream
+    // time between consecutive events goes to the stage of the first.  Events come from a pool that grows
+    // with the longest loop seen; nothing is read back before the loop has ended.
+    std::vector<hipEvent_t> st_ev;
+    std::vector<int> st_id;
+    bool st_on = false;
+
+    // ---- point depths and the chirality veto (depth.hpp): the state that depth_host.hpp builds and uses.  It lives
+    // here because the damping loops consult the veto (vetoed()).
+    struct DepthPlan {
+        bool ready = false;
+        DevBuf<int64_t> cm_col;
+        DevBuf<long long> chunk_col;
+        DevBuf<unsigned long long> red;                  // [0] count, [1] smallest key, [2, 2 + nc) per image, then per chunk
+        DevBuf<double> depth;
+        std::vector<unsigned long long> img_host;
+        EventTimer<1> timer;                             // last point_depths: reset of the scratch + the two kernels
+    } dep;
+    // The built-in chirality veto (dbat_hip_set_chirality): at every trial point a damping loop consults its veto at,
+    // the number of observations with !(depth > chir_thr) at zt; a non-zero count rejects.  Two words cross to the host
+    // (the count and the smallest depth, kept for dbat_hip_chirality_stats), the parameter vector never does.
+    bool chirality = false;
+    double chir_thr = 0.0;
+    int64_t veto_tested = 0, veto_rejected = 0, veto_n_behind = 0;
+    double veto_min_depth = NAN;
+
+    // ======== methods ========
+    template <class F> void with_model(F &&f) { with_value<2, 3, 4, 5>(P.model, f); }     // f(integral_constant): the lens model of the plan
     bool multi() const { return nccl != nullptr || allreduce != nullptr; }
-    // kernels with more than 64 KiB of dynamic LDS must opt in on the device: the ones this handle has opted in, and
-    // at what size (a handle's launches run on its one device; a handle opts in at most 5 kernels)
-    struct { const void *kernel; size_t bytes; } lds_opt_in[8] = {};
-    int n_lds_opt_in = 0;
     // a kernel launch on the handle's stream
     template <auto K, class... A>
     void launch(dim3 grid, dim3 block, size_t lds, A &&...args) {
@@ -255,14 +330,6 @@ struct Core {
         }
         dbat::launch<K>(grid, block, lds, stream, std::forward<A>(args)...);
     }
-    // linearisation state
-    double f_lin = 0, trace_jtj = 0, lambda_lin = 0;
-    int scale_lin = 0;
-    bool have_lin = false;
-    bool s_valid = false;      // S holds an unfactorised reduced system
-    bool s_dense_dirty = true; // S may hold non-zeros outside its envelope (fresh allocation, dense inverse)
-    // counters
-    int n_res_evals = 0, n_lin = 0, n_solves = 0, n_trace_only = 0;
 
     ~Core() {
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
@@ -492,8 +559,8 @@ struct Core {
 
     // dbat_hip_set_values: new parameter values / prior observations for the same structure.  The host plan has them
     // already (plan_set_values); here the device copies, and everything a previous solve left behind is forgotten.
+    // (The caller has dropped the robust reweighting first: robust_host.hpp robust_reset.)
     void set_values(bool io_changed) {
-        robust_reset();
         HIPCHK(hipMemcpyAsync(z.p, P.z0.data(), P.NZ * 8, hipMemcpyHostToDevice, stream));
         HIPCHK(hipMemcpyAsync(io_fixed.p, P.io_fixed.data(), P.io_fixed.size() * 8, hipMemcpyHostToDevice, stream));
         if (d.any_prior) {
@@ -546,10 +613,6 @@ struct Core {
     }
 
     // ---- helpers
-    bool lin_pending = false;                        // k_finish's scalars are in the mailbox (or on their way), not read yet
-    bool det_timeout_pending = false;                // ... and the timeout count of the deterministic signature kernel
-    unsigned long long mb_seq = 0;                   // ticket of the last kernel that reports through mailbox slot 63
-    bool mb_armed = false;                           // ... and such a kernel is the last one enqueued
     void sync() {
         // The kernel that ends a phase writes this wait's ticket into the mailbox after its results: spin on
         // it (a few microseconds after the kernel's last store) instead of sleeping in
@@ -588,12 +651,7 @@ struct Core {
         }
     }
     void mark(int i) { if (timing) HIPCHK(hipEventRecord(kev[i], stream)); }
-    // ---- stage timers of a solve (dbat_hip_result.stage_s): an event where a stage is enqueued; the stream
-    // time between consecutive events goes to the stage of the first.  Events come from a pool that grows
-    // with the longest loop seen; nothing is read back before the loop has ended.
-    std::vector<hipEvent_t> st_ev;
-    std::vector<int> st_id;
-    bool st_on = false;
+    // ---- stage timers of a solve (st_ev, st_id above)
     void stage(int id) {
         if (!st_on) return;
         if (st_id.size() == st_ev.size()) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); st_ev.push_back(e); }
@@ -669,13 +727,7 @@ struct Core {
         sync();
     }
 
-    // ---- The parameter trace of a damping loop (bundle.m's T: x of every iteration), kept ON THE DEVICE while the loop
-    // runs -- one gather kernel per column, no copy and no wait -- and brought down once at the end.  (Round 5 fetched
-    // every column when it was made: a 24 MB copy into pageable memory and a synchronisation per iteration at C3, then a
-    // second copy into the caller's array.)  Columns a loop never wrote come back as NaN.
-    DevBuf<double> trace_dev;
-    int trace_cap = 0, trace_n = 0;
-    std::vector<uint8_t> trace_have;
+    // ---- the parameter trace of a damping loop, on the device (trace_dev above)
     void trace_begin() { trace_n = 0; trace_have.clear(); }
     void trace_put(int k, const double *z_dev) {       // column k <- x(z_dev); collective on a sharded handle
         if (!P.n || k < 0) return;
@@ -934,15 +986,7 @@ struct Core {
         if (d.ablate & 32) dump_phase_profiles();
         build_tail_enqueue(zz, pl.total);
     }
-    // A linearisation at z that a damping loop has asked for but nobody has needed yet.  levenberg_marquardt.m
-    // (:189-194) and levenberg_marquardt_powell.m linearise at every ACCEPTED point before they test for
-    // termination; after the last accepted step that Jacobian is only returned (final.weighted.J), never
-    // used for a step.  Here it is built when the next solve -- or a caller who wants the gradient, the
-    // column norms or J v -- asks for it, and not at all otherwise: one build kernel chain less per solve
-    // (C3: 6 -> 5 linearisations for 4 LM iterations).  The iterates are the same, bit for bit.
-    bool pend_build = false;
-    double pend_lambda = 0;
-    int pend_scale = 0;
+    // a linearisation at z that is built only when somebody needs it (pend_build above)
     void request_build(double lambda, int scale) {
         pend_build = true; pend_lambda = lambda; pend_scale = scale;
         lambda_lin = lambda; scale_lin = scale;
@@ -1009,7 +1053,6 @@ struct Core {
         have_lin = s_valid = !trace_only;
         if (!trace_only) ++n_lin; else ++n_trace_only;
     }
-    bool replicate_next = false;     // domain mode: the next build sums the whole matrix after k_finish (in-place factorisation)
     // sum of the envelope of S (incl. the right-hand-side row) over the ranks, after k_finish
     void allreduce_matrix() {
         if (!pk.p) pk.alloc((size_t)(pk_s_count + 3 * P.NS + 8));
@@ -1091,11 +1134,6 @@ struct Core {
     // near_singular mimics MATLAB's 'nearlySingularMatrix' warning through
     // CHOLMOD's estimate rcond = (min diag(L) / max diag(L))^2 < eps over the
     // pivots of the point blocks and of the reduced system.
-    bool near_singular = false;
-    const bool pivot_stats = env_on("DBAT_HIP_PIVOT_STATS");
-    double rcond_est = 0.0;      // (min pivot / max pivot)^2 of the last solve; 0 after a failed factorisation
-    int chol_info = 0;           // k_chol_df's info of the last solve: > 0 first non-positive pivot, -1 dataflow abort
-    double piv_last[4] = {0, 0, 0, 0};   // {min, max} pivot of the point blocks, {min, max} of the reduced system
     bool solve(double &JpJp, double &rJp, double &pp) {
         ensure_build();
         if (!s_valid) build(zlin.p, lambda_lin, scale_lin);   // the factorisation overwrote S
@@ -1141,307 +1179,29 @@ struct Core {
                     mm[0], mm[1], mm[2], mm[3], hinfo, rcond_est);
         return failed;
     }
-    // ---- posterior covariance blocks at z (bundle_cov.m): s0^2 * blocks of inv(J'J)
-    std::vector<double> cop_tmp;
-    // The set-up shared by posterior_cov and redundancy: the unscaled, undamped reduced system at z (and V^-1 per
-    // point), factored, and inv(S).  On one rank, from the compact nested-dissection factor, only the entries the blocks
-    // need (selected inversion, chol_df.hpp) -- no dense inverse (C4: 7.2 GB and 9 TF of rocsolver_dpotri).  The dense
-    // inverse remains for several ranks, for problems without the compact factor (shared EO blocks, DBAT_HIP_ND_OFF)
-    // and for a caller who asks for it (want_dense).  Leaves the camera records at z.
-    SinvView inverse_at_z(bool want_dense) {
-        const bool selinv = use_perm && !multi() && !want_dense && dfchol.selinv_supported() && !env_on("DBAT_HIP_COV_DENSE");
-        replicate_next = !selinv;                    // (domain sharding: the whole system on every rank for this one)
-        try { build(z.p, 0.0, 0); } catch (...) { replicate_next = false; throw; }   // unscaled, undamped reduced system + V^-1 per point
-        replicate_next = false;
-        s_valid = false;
-        SinvView SV;
-        int hinfo = 0;
-        if (selinv) {
-            factor_solve_enqueue();                  // the compact factor (S itself is only read)
-            HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(hinfo), hipMemcpyDeviceToHost, stream));
-            sync();
-            if (hinfo != 0) throw DeviceError{"posterior covariance: the reduced normal matrix is not positive definite"};
-            if (!dfchol.selected_inverse(stream, linv.p)) throw DeviceError{"out of device memory (selected inverse)"};
-            HIPCHK(hipGetLastError());
-            SV.tiles = dfchol.d_ztiles; SV.toff = dfchol.d_toff; SV.perm = dfchol.d_perm; SV.nT = dfchol.nT;
-        } else {
-            chol_in_place = true;
-            // the in-place factorisation stores whole 64 x 64 tiles, which straddle the column envelope that the
-            // next build clears: from here on S must be cleared densely -- also when the factorisation fails
-            s_dense_dirty = true;
-            factor_solve_enqueue();                  // L in the lower triangle of S
-            chol_in_place = false;
-            HIPCHK(hipMemcpyAsync(&hinfo, info.p, sizeof(hinfo), hipMemcpyDeviceToHost, stream));
-            sync();
-            if (hinfo != 0) throw DeviceError{"posterior covariance: the reduced normal matrix is not positive definite"};
-            if (!blas) {     // (created on first use: rocblas_create_handle costs 0.1 s, and only the dense inverse needs it)
-                if (rocblas_create_handle(&blas) != rocblas_status_success) throw DeviceError{"rocblas_create_handle failed"};
-                rocblas_set_stream(blas, stream);
-            }
-            if (rocsolver_dpotri(blas, rocblas_fill_lower, (rocblas_int)P.NS, S, (rocblas_int)ldS, info.p) != rocblas_status_success)
-                throw DeviceError{"rocsolver_dpotri failed"};
-            SV.dense = S; SV.ld = ldS;
-        }
-        have_lin = false;
-        prep_cams(z.p);
-        return SV;
-    }
-    void posterior_cov(double s0, double *hCEO, double *hCIO, double *hCOP, double *hSinv) {
-        const SinvView SV = inverse_at_z(hSinv != nullptr);
-        const double s02 = s0 * s0;
-        DevBuf<double> dCEO, dCIO, dCOP;
-        if (hCEO) dCEO.alloc((size_t)36 * P.nc);
-        if (hCIO && P.nIOu > 0) dCIO.alloc((size_t)P.nIOu * P.nIOu);
-        if (hCEO || (hCIO && P.nIOu > 0)) {
-            const int64_t tot = 36 * (int64_t)P.nc + (int64_t)P.nIOu * P.nIOu;
-            launch<k_cov_cam>(dim3((unsigned)cdiv(tot, 256)), dim3(256), 0, d, SV, s02, dCEO.p, dCIO.p);
-        }
-        if (hCOP) {
-            dCOP.alloc((size_t)9 * P.np);
-            HIPCHK(hipMemsetAsync(dCOP.p, 0, (size_t)9 * P.np * sizeof(double), stream));
-            with_model([&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
-                if (nb > 0) launch<k_cov_points<M, IO>>(dim3((unsigned)nb), dim3(P.BT), lds_cov, d, z.p, cams.p, Vinv.p, SV, s02, dCOP.p, HatOut{});
-                if (ngiant > 0) launch<k_cov_giant<M, IO>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, z.p, cams.p, Vinv.p, SV, s02, dCOP.p, HatOut{});
-            }); });
-            if (multi()) do_allreduce(dCOP.p, (int64_t)9 * P.np);   // blocks of the other shards' points
-            cop_tmp.resize((size_t)9 * P.np);
-            HIPCHK(hipMemcpyAsync(cop_tmp.data(), dCOP.p, (size_t)9 * P.np * sizeof(double), hipMemcpyDeviceToHost, stream));
-        }
-        if (hCEO) HIPCHK(hipMemcpyAsync(hCEO, dCEO.p, (size_t)36 * P.nc * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (hCIO && P.nIOu > 0) HIPCHK(hipMemcpyAsync(hCIO, dCIO.p, (size_t)P.nIOu * P.nIOu * sizeof(double), hipMemcpyDeviceToHost, stream));
-        if (hSinv)                                   // full inv(S) (lower triangle valid), NS x NS column-major, not scaled by s0^2
-            HIPCHK(hipMemcpy2DAsync(hSinv, (size_t)P.NS * sizeof(double), S, (size_t)ldS * sizeof(double),
-                                    (size_t)P.NS * sizeof(double), (size_t)P.NS, hipMemcpyDeviceToHost, stream));
-        sync();
-        if (hCOP)                                    // device blocks are in processing order
-            for (int64_t p = 0; p < P.np; ++p)
-                std::copy(cop_tmp.begin() + 9 * (int64_t)P.pt_rank[p], cop_tmp.begin() + 9 * (int64_t)P.pt_rank[p] + 9, hCOP + 9 * p);
-    }
-    // ---- reliability at z: Qvv = I - J inv(J'J) J' on the image rows (2 x 2 per image point, caller's order: r_u, q_uv,
-    // r_v) and the redundancy numbers r = 1 - w_p C(p, p) of the prior rows (dbat_hip_final_residuals' row order)
-    void redundancy(double *hqvv, double *hrp) {
-        const SinvView SV = inverse_at_z(false);
-        const int64_t nprior = (int64_t)P.prior_z.size();
-        DevBuf<double> qvv, dCz, Ccc, gscr, rp;
-        DevBuf<int64_t> pz;
-        qvv.alloc((size_t)3 * std::max<int64_t>(P.no, 1));
-        dCz.alloc((size_t)P.NZ);
-        Ccc.alloc((size_t)P.nc * P.ncolmax * P.ncolmax);
-        HIPCHK(hipMemsetAsync(qvv.p, 0, (size_t)3 * P.no * sizeof(double), stream));
-        HIPCHK(hipMemsetAsync(dCz.p, 0, (size_t)P.NZ * sizeof(double), stream));
-        const int64_t nCcc = (int64_t)P.nc * P.ncolmax * P.ncolmax;
-        if (nCcc > 0) launch<k_hat_cam_blocks>(dim3((unsigned)cdiv(nCcc, 256)), dim3(256), 0, d, cams.p, SV, Ccc.p);
-        HatOut hat;
-        hat.Ccc = Ccc.p; hat.qvv = qvv.p; hat.dCz = dCz.p;
-        if (ngiant > 0) {
-            gscr.alloc((size_t)(P.giant_start.back() - P.giant_start.front()) * 9);
-            hat.gscr = gscr.p;
-        }
-        with_model([&](auto M) { with_value<false, true>(P.with_io, [&](auto IO) {
-            if (nb > 0) launch<k_cov_points<M, IO, true>>(dim3((unsigned)nb), dim3(P.BT), lds_cov, d, z.p, cams.p, Vinv.p, SV, 1.0, (double *)nullptr, hat);
-            if (ngiant > 0) launch<k_cov_giant<M, IO, true>>(dim3((unsigned)ngiant), dim3(giant_threads), 0, d, z.p, cams.p, Vinv.p, SV, 1.0, (double *)nullptr, hat);
-        }); });
-        if (multi()) {                               // the other shards' observations and points
-            do_allreduce(qvv.p, 3 * P.no);
-            do_allreduce(dCz.p + P.NS, P.NZ - P.NS);
-        }
-        if (nprior > 0) {
-            rp.alloc((size_t)nprior);
-            pz.alloc((size_t)nprior);
-            HIPCHK(hipMemcpyAsync(pz.p, P.prior_z.data(), (size_t)nprior * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-            launch<k_hat_prior>(dim3((unsigned)cdiv(nprior, 256)), dim3(256), 0, d, SV, pz.p, nprior, dCz.p, rp.p);
-            HIPCHK(hipMemcpyAsync(hrp, rp.p, (size_t)nprior * sizeof(double), hipMemcpyDeviceToHost, stream));
-        }
-        HIPCHK(hipMemcpyAsync(hqvv, qvv.p, (size_t)3 * P.no * sizeof(double), hipMemcpyDeviceToHost, stream));
-        sync();
-    }
-    // camera-major slot of every owned observation (processing order): the plan's stable counting sort by camera, tiled
-    // part first
-    std::vector<int32_t> cm_slots() const {
-        std::vector<int32_t> cmm((size_t)nobs);
-        const int64_t ntiled = P.nb_tiled > 0 ? P.batch_start[P.nb_tiled] : 0;
-        std::vector<int64_t> cnt((size_t)P.nc + 1);
-        for (int part = 0; part < 2; ++part) {
-            const int64_t lo = part ? ntiled : 0, hi = part ? nobs : ntiled;
-            std::fill(cnt.begin(), cnt.end(), 0);
-            for (int64_t o = lo; o < hi; ++o) ++cnt[P.o_cam[o] + 1];
-            for (int c = 0; c < P.nc; ++c) cnt[c + 1] += cnt[c];
-            for (int64_t o = lo; o < hi; ++o) cmm[o] = (int32_t)(lo + cnt[P.o_cam[o]]++);
-        }
-        return cmm;
-    }
-    // ---- point depths and the chirality veto (depth.hpp): the state that depth_host.hpp builds and uses.  It lives
-    // here because the damping loops consult the veto (vetoed()).
-    struct DepthPlan {
-        bool ready = false;
-        DevBuf<int64_t> cm_col;
-        DevBuf<long long> chunk_col;
-        DevBuf<unsigned long long> red;                  // [0] count, [1] smallest key, [2, 2 + nc) per image, then per chunk
-        DevBuf<double> depth;
-        std::vector<unsigned long long> img_host;
-        EventTimer<1> timer;                             // last point_depths: reset of the scratch + the two kernels
-    } dep;
-    // The built-in chirality veto (dbat_hip_set_chirality): at every trial point a damping loop consults its veto at,
-    // the number of observations with !(depth > chir_thr) at zt; a non-zero count rejects.  Two words cross to the host
-    // (the count and the smallest depth, kept for dbat_hip_chirality_stats), the parameter vector never does.
-    bool chirality = false;
-    double chir_thr = 0.0;
-    int64_t veto_tested = 0, veto_rejected = 0, veto_n_behind = 0;
-    double veto_min_depth = NAN;
     void veto_stats_reset() { veto_tested = veto_rejected = veto_n_behind = 0; veto_min_depth = NAN; }
     bool chirality_veto();                               // right after eval_f_step (depth_host.hpp)
-    // ---- robust reweighting (robust.hpp).  A handle that never sees a robust call has none of this: pw follows the
-    // plan (uniform weights: the camera records' weights, no o_w / sg_w / cm_w).  robust_promote() gives every owned
-    // observation its own weights (o_w = o_w_base * sqrt(omega)) and keeps the maps from processing order to the
-    // slot-major (sg_map, -1: no slot) and camera-major (cm_map) copies; robust_reset() returns to the fresh handle.
-    bool pw = false;                    // the kernels read per-observation weights (o_w, sg_w, cm_w)
-    bool robust_on = false;
-    DevBuf<double> o_w_base, omega, rsel_hist_f, rsel_red, robust_r;
-    DevBuf<uint64_t> rs_bits, rsel_state;
-    DevBuf<int32_t> sg_map, cm_map;
-    DevBuf<unsigned> rsel_hist;
-    DevBuf<unsigned long long> rmax;
+    // The weights the engine's kernels read, switched as a whole and nowhere else after init(): per_obs gives every owned
+    // observation its own pair in o_w and its slot-major (sg_w; slots outside the groups stay 0) and camera-major
+    // (cm_w) copies -- their contents are the caller's to fill (robust_host.hpp) --, !per_obs returns to the plan's
+    // (uniform weights: the camera records' weights and no copies).  Work in flight reads the old ones: waited for.
     template <class T> static void dev_free(DevBuf<T> &b) { DevBuf<T> t; std::swap(t.p, b.p); b.n = 0; }
-    unsigned robust_grid() const { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(nobs, 256), 4096)); }
-    void robust_scratch() {             // what an evaluation needs (dbat_hip_robust_weights does not promote)
-        if (rs_bits.p || rsel_state.p) return;
-        rs_bits.alloc((size_t)std::max<int64_t>(nobs, 1));
-        robust_r.alloc((size_t)2 * std::max<int64_t>(P.no, 1));
-        rsel_hist.alloc(2 * RSEL_BINS); rsel_hist_f.alloc(2 * RSEL_BINS);
-        HIPCHK(hipMemset(rsel_hist.p, 0, 2 * RSEL_BINS * sizeof(unsigned)));
-        rsel_state.alloc(4); rmax.alloc(1); rsel_red.alloc((size_t)P.nranks);
-    }
-    void robust_promote() {
-        if (robust_on) return;
-        if (nobs >= ((int64_t)1 << 31) / 2) throw UsageError{"robust weights: more than 2^30 observations on one rank"};
-        robust_scratch();
+    void obs_weights(bool per_obs) {
+        const bool sig = route == TileRoute::sig;
         const size_t n2 = (size_t)2 * std::max<int64_t>(nobs, 1);
-        o_w_base.alloc(n2);
-        if (P.uniform_w) {
+        if (!per_obs) HIPCHK(hipStreamSynchronize(stream));
+        if (P.uniform_w && per_obs) {
             o_w.alloc(n2); cm_w.alloc(n2);
-            if (route == TileRoute::sig) { sg_w.alloc(n2); HIPCHK(hipMemsetAsync(sg_w.p, 0, n2 * sizeof(double), stream)); }   // slots outside the groups stay 0
-            if (nobs > 0) launch<k_robust_base>(dim3(robust_grid()), dim3(256), 0, nobs, (const int32_t *)o_cam.p, (const double *)cam_w.p, o_w_base.p);
-        } else if (nobs > 0) {
-            HIPCHK(hipMemcpyAsync(o_w_base.p, o_w.p, (size_t)2 * nobs * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            if (sig) { sg_w.alloc(n2); HIPCHK(hipMemsetAsync(sg_w.p, 0, n2 * sizeof(double), stream)); }
+        } else if (P.uniform_w) {
+            dev_free(o_w); dev_free(cm_w);
+            if (sig) dev_free(sg_w);
+        } else if (!per_obs) {   // as init() uploaded them
+            HIPCHK(hipMemcpy(o_w.p, P.o_w.data(), P.o_w.size() * sizeof(double), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(cm_w.p, P.cm_w.data(), P.cm_w.size() * sizeof(double), hipMemcpyHostToDevice));
+            if (sig) HIPCHK(hipMemcpy(sg_w.p, P.sg_w.data(), P.sg_w.size() * sizeof(double), hipMemcpyHostToDevice));
         }
-        cm_map.upload(cm_slots());
-        if (route == TileRoute::sig) {   // slot-major slot: group g, slot j, point i at obs0_g + j*m_g + i (plan.hpp, signature groups)
-            std::vector<int32_t> sgm((size_t)nobs, -1);
-            for (size_t q = 0; q < P.sg_chunk.size() / 8; ++q) {
-                const int32_t *ch = &P.sg_chunk[8 * q];
-                const int64_t npts = ch[1], k = ch[2], m = ch[4], i0 = ch[5], g0 = ch[6];
-                for (int64_t i = i0; i < i0 + npts; ++i)
-                    for (int64_t j = 0; j < k; ++j) sgm[g0 + i * k + j] = (int32_t)(g0 + j * m + i);
-            }
-            sg_map.upload(sgm);
-        }
-        omega.alloc((size_t)std::max<int64_t>(nobs, 1));
-        robust_on = true; pw = true; d.o_w = o_w.p;
-        robust_set_ones();
-    }
-    void robust_apply_omega() {         // o_w, sg_w, cm_w from omega
-        if (nobs > 0)
-            launch<k_robust_apply<false>>(dim3(robust_grid()), dim3(256), 0, nobs, (const uint64_t *)nullptr, 1.0, 0, 1.0, omega.p, (const double *)o_w_base.p, o_w.p,
-                                          (const int32_t *)(route == TileRoute::sig ? sg_map.p : nullptr), sg_w.p, (const int32_t *)cm_map.p, cm_w.p);
-        s_valid = false;
-    }
-    void robust_set_ones() {
-        if (nobs > 0) launch<k_robust_fill>(dim3(robust_grid()), dim3(256), 0, nobs, 1.0, omega.p);
-        robust_apply_omega();
-    }
-    void robust_reset() {
-        if (robust_on) {
-            HIPCHK(hipStreamSynchronize(stream));
-            if (P.uniform_w) {
-                dev_free(o_w); dev_free(cm_w);
-                if (route == TileRoute::sig) dev_free(sg_w);
-                d.o_w = nullptr;
-            } else {             // the plan's weights, as init() uploaded them
-                HIPCHK(hipMemcpy(o_w.p, P.o_w.data(), P.o_w.size() * sizeof(double), hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(cm_w.p, P.cm_w.data(), P.cm_w.size() * sizeof(double), hipMemcpyHostToDevice));
-                if (route == TileRoute::sig) HIPCHK(hipMemcpy(sg_w.p, P.sg_w.data(), P.sg_w.size() * sizeof(double), hipMemcpyHostToDevice));
-            }
-            dev_free(o_w_base); dev_free(omega); dev_free(sg_map); dev_free(cm_map);
-            robust_on = false; pw = !P.uniform_w; s_valid = false;
-        }
-        dev_free(rs_bits); dev_free(robust_r); dev_free(rsel_hist); dev_free(rsel_hist_f); dev_free(rsel_state); dev_free(rmax); dev_free(rsel_red);
-    }
-    // max of one double over the ranks (the all-reduce sums: every rank contributes its own slot)
-    double max_over_ranks(double v) {
-        if (!multi()) return v;
-        std::vector<double> h((size_t)P.nranks, 0.0);
-        h[P.rank] = v;
-        HIPCHK(hipMemcpyAsync(rsel_red.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-        do_allreduce(rsel_red.p, P.nranks);
-        HIPCHK(hipMemcpyAsync(h.data(), rsel_red.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        return *std::max_element(h.begin(), h.end());
-    }
-    // exact median of s over all ranks' observations: radix select of the two middle order statistics
-    double robust_median() {
-        const uint64_t total = (uint64_t)P.no;
-        uint64_t st[4] = {0, 0, (total - 1) / 2, total / 2};
-        HIPCHK(hipMemcpyAsync(rsel_state.p, st, sizeof st, hipMemcpyHostToDevice, stream));
-        const unsigned gh = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(nobs, 4096), 1024));
-        for (int pass = 0; pass < RSEL_PASSES; ++pass) {
-            if (nobs > 0) launch<k_rsel_hist>(dim3(gh), dim3(256), 0, nobs, (const uint64_t *)rs_bits.p, (const uint64_t *)rsel_state.p, RSEL_SHIFT[pass], RSEL_BITS[pass], rsel_hist.p);
-            if (multi()) {
-                launch<k_rsel_to_f64>(dim3(16), dim3(256), 0, rsel_hist.p, rsel_hist_f.p);
-                do_allreduce(rsel_hist_f.p, 2 * RSEL_BINS);
-                launch<k_rsel_pick<true>>(dim3(1), dim3(256), 0, rsel_hist.p, (const double *)rsel_hist_f.p, rsel_state.p, RSEL_SHIFT[pass]);
-            } else {
-                launch<k_rsel_pick<false>>(dim3(1), dim3(256), 0, rsel_hist.p, (const double *)nullptr, rsel_state.p, RSEL_SHIFT[pass]);
-            }
-        }
-        HIPCHK(hipMemcpyAsync(st, rsel_state.p, sizeof st, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        double a, b;
-        memcpy(&a, &st[0], 8); memcpy(&b, &st[1], 8);
-        return (a + b) / 2.0;
-    }
-    // One evaluation at zz (collective): s of every owned observation (rs_bits), the scale, omega' and max |omega' -
-    // omega| over all ranks.  s_ip / omega_ip (device, [no], zero outside this rank's observations): optional.
-    void robust_eval(const double *zz, const dbat_hip_robust_options &ro, double *s_ip, double *omega_ip, double &scale, double &maxchg) {
-        robust_scratch();
-        HIPCHK(hipMemsetAsync(robust_r.p, 0, (size_t)2 * P.no * sizeof(double), stream));
-        eval_f(zz, nullptr, robust_r.p);
-        if (nobs > 0)
-            launch<k_robust_norm>(dim3(robust_grid()), dim3(256), 0, nobs, (const int64_t *)o_row.p, (const double *)robust_r.p,
-                                  (const double *)(robust_on ? o_w_base.p : (P.uniform_w ? nullptr : o_w.p)), (const int32_t *)o_cam.p, (const double *)cam_w.p, rs_bits.p, s_ip);
-        scale = 1.0;
-        if (ro.scale == DBAT_HIP_SCALE_MAD && P.no > 0) {
-            scale = robust_median() / ROBUST_MAD_C;
-            if (scale == 0.0) scale = 1.0;
-        }
-        HIPCHK(hipMemsetAsync(rmax.p, 0, sizeof(unsigned long long), stream));
-        if (nobs > 0)
-            launch<k_robust_weight>(dim3(robust_grid()), dim3(256), 0, nobs, (const uint64_t *)rs_bits.p, scale, (int)ro.loss, ro.k,
-                                    (const double *)(robust_on ? omega.p : nullptr), (const int64_t *)o_row.p, omega_ip, rmax.p);
-        unsigned long long mb = 0;
-        HIPCHK(hipMemcpyAsync(&mb, rmax.p, sizeof mb, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        memcpy(&maxchg, &mb, 8);
-        maxchg = max_over_ranks(maxchg);
-    }
-    // apply the omega' of the last evaluation (same scale and loss)
-    void robust_apply_eval(const dbat_hip_robust_options &ro, double scale) {
-        robust_promote();
-        if (nobs > 0)
-            launch<k_robust_apply<true>>(dim3(robust_grid()), dim3(256), 0, nobs, (const uint64_t *)rs_bits.p, scale, (int)ro.loss, ro.k, omega.p,
-                                         (const double *)o_w_base.p, o_w.p, (const int32_t *)(route == TileRoute::sig ? sg_map.p : nullptr), sg_w.p,
-                                         (const int32_t *)cm_map.p, cm_w.p);
-        s_valid = false;
-    }
-    // omega in IP order on every rank (1 everywhere on a handle that was not promoted)
-    void robust_omega_ip(double *host) {
-        if (!robust_on) { std::fill(host, host + P.no, 1.0); return; }
-        DevBuf<double> t;
-        t.alloc((size_t)std::max<int64_t>(P.no, 1));
-        HIPCHK(hipMemsetAsync(t.p, 0, (size_t)P.no * sizeof(double), stream));
-        if (nobs > 0) launch<k_scatter_rows1>(dim3(robust_grid()), dim3(256), 0, nobs, (const int64_t *)o_row.p, (const double *)omega.p, t.p);
-        if (multi()) do_allreduce(t.p, P.no);
-        HIPCHK(hipMemcpyAsync(host, t.p, (size_t)P.no * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
+        pw = per_obs || !P.uniform_w; d.o_w = pw ? o_w.p : nullptr; s_valid = false;
     }
     // ||J v||^2 and r'Jv at the linearisation point, ||v||^2 over owned entries
     void jtimes(const double *v, double &JvJv, double &rJv, double &vv) {
@@ -1748,7 +1508,54 @@ static void loop_lmp(Core &c, const dbat_hip_options &o, double delta0, LoopOut 
     c.settle_lin_point();
 }
 
-struct PointIndex; struct AnglePlan; struct QualPlan;         // analysis_host.hpp, angles_host.hpp, quality_host.hpp
+static void solve_once(Core &c, const dbat_hip_options *opt, double *x, dbat_hip_result *result, double *res, double *damp,
+                       double *aux, double *trace) {
+    c.n_res_evals = c.n_lin = c.n_solves = c.n_trace_only = 0;
+    c.veto_stats_reset();
+    c.trace_begin();
+    c.x_to_z(x, c.z.p);
+    c.lambda_lin = NAN;
+    LoopOut out;
+    const auto t0 = std::chrono::steady_clock::now();
+    c.stages_begin();
+    struct StageGuard { Core &c; ~StageGuard() { c.st_on = false; } } stage_guard{c};     // (a loop that throws must not leave the timers on)
+    switch (opt->damping) {
+        case DBAT_HIP_DAMP_GM: loop_gm(c, *opt, out); break;
+        case DBAT_HIP_DAMP_GNA: loop_gna(c, *opt, out); break;
+        case DBAT_HIP_DAMP_LM: loop_lm(c, *opt, out); break;
+        default: {
+            double delta0 = opt->delta0;
+            if (!(delta0 > 0)) {                                   // bundle.m:325 delta0 = norm(x0)
+                double s = 0;
+                for (int64_t i = 0; i < c.P.n; ++i) s += x[i] * x[i];
+                delta0 = std::sqrt(s);
+            }
+            loop_lmp(c, *opt, delta0, out);
+        }
+    }
+    c.sync();
+    result->time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    c.stages_end(result->stage_s);
+    result->code = out.code; result->iters = out.iters;
+    c.z_to_x(c.z.p, x);
+    const int cap_res = opt->max_iter + 3, cap_d = 2 * opt->max_iter + 4;
+    result->n_res = (int)std::min<size_t>(out.res.size(), cap_res);
+    if (res) for (int i = 0; i < result->n_res; ++i) res[i] = out.res[i];
+    result->n_damp = (int)std::min<size_t>(out.damp.size(), cap_d);
+    if (damp) for (int i = 0; i < result->n_damp; ++i) damp[i] = out.damp[i];
+    if (aux) for (int i = 0; i < cap_d; ++i) aux[i] = i < (int)out.aux.size() ? out.aux[i] : NAN;
+    result->n_trace = 0;
+    if (opt->store_trace && trace) {
+        const int cap_t = opt->max_iter + 2;
+        result->n_trace = c.trace_download(trace, cap_t);
+    }
+    const double dof = (double)(c.P.m - c.P.n);
+    result->sigma0 = std::sqrt(2 * out.f_final / dof);            // bundle.m:476-483
+    result->n_residual_evals = c.n_res_evals; result->n_linearizations = c.n_lin; result->n_solves = c.n_solves;
+    result->n_trace_only = c.n_trace_only;
+}
+
+struct PointIndex; struct AnglePlan; struct QualPlan; struct RobustState;     // analysis_host.hpp, angles_host.hpp, quality_host.hpp, robust_host.hpp
 
 }  // namespace dbat
 
@@ -1763,6 +1570,8 @@ struct dbat_hip_handle {
     std::unique_ptr<PointIndex> pts;
     std::unique_ptr<AnglePlan> ang;
     std::unique_ptr<QualPlan> qual;
+    // what the robust reweighting needs, from the first robust call until the weights are reset
+    std::unique_ptr<RobustState> rob;
     __attribute__((visibility("hidden"))) ~dbat_hip_handle() = default;     // (no symbol of the ABI)
 };
 
@@ -1774,11 +1583,30 @@ struct dbat_hip_handle {
     catch (const std::bad_alloc &) { g_err = "out of host memory"; return DBAT_HIP_ENOMEM; } \
     catch (const std::exception &e) { g_err = e.what(); return DBAT_HIP_EINVAL; }
 
-// ---- the network analyses: plan, drivers and C entry points of each beside its kernels (the transforms: at the end) ----
+namespace dbat {
+static const char *solve_args_error(const dbat_hip_handle *h, const dbat_hip_options *opt, const double *x, const dbat_hip_result *result,
+                                    const double *trace, int &rc) {
+    rc = DBAT_HIP_EINVAL;
+    if (!h || !opt || !x || !result) return "null argument";
+    if (opt->damping < 0 || opt->damping > 3) return "Unknown damping";
+    if (opt->store_trace && !trace) return "store_trace without a trace buffer";
+    rc = DBAT_HIP_EUNSUPPORTED;
+    if (opt->term_fun && h->core->P.nranks > 1) return "term_fun: one-rank handles only (J*p rows stay with their shard)";
+    return nullptr;
+}
+}  // namespace dbat
+
+// ---- everything that is not the engine: state, drivers and C entry points of each feature beside its kernels
+// ("Source map"; the transforms and the relative orientation take no handle: at the end) ----
 #include "analysis_host.hpp"
+#include "robust_host.hpp"        // (cm_slots: before depth_host.hpp)
 #include "angles_host.hpp"
 #include "depth_host.hpp"
 #include "quality_host.hpp"
+#include "cov_host.hpp"
+#include "export_host.hpp"
+#include "initial_host.hpp"
+#include "debug_host.hpp"
 
 extern "C" {
 
@@ -1944,6 +1772,7 @@ int dbat_hip_set_values(dbat_hip_handle *h, const dbat_hip_problem *prob) {
     const size_t nio = (size_t)c.P.nIOrows * c.P.nc;
     const bool io_changed = memcmp(c.P.io_fixed.data(), prob->IO_val, nio * sizeof(double)) != 0;
     if (!plan_set_values(*prob, c.P)) { g_err = c.P.err; return DBAT_HIP_EINVAL; }
+    robust_reset(*h);
     c.set_values(io_changed);
     return DBAT_HIP_OK;
     API_CATCH
@@ -1982,207 +1811,6 @@ int dbat_hip_structural_rank_ok(const dbat_hip_handle *h, int32_t *ok) {
     return DBAT_HIP_OK;
 }
 
-namespace dbat {
-static void export_residuals(Core &c, const double *zdev, double *r_unw, double *r_wgt, double *f) {
-    // image rows via k_residual (reference row order), prior rows on the host
-    DevBuf<double> tmp;
-    double *dev_unw = nullptr;
-    if (r_unw || r_wgt) { tmp.alloc(2 * std::max<int64_t>(c.P.no, 1)); dev_unw = tmp.p; HIPCHK(hipMemsetAsync(dev_unw, 0, 2 * c.P.no * 8, c.stream)); }
-    const double ff = c.eval_f(zdev, nullptr, dev_unw);
-    if (f) *f = ff;
-    if (!(r_unw || r_wgt)) return;
-    const Plan &P = c.P;
-    // a sharded handle computes the rows of its own observations; the sum over the ranks
-    // (zeros elsewhere) gives every rank the whole vector.  Weighted rows on the device
-    // as well, so that the weights of the other shards' observations are not needed here.
-    DevBuf<double> tmpw;
-    if (r_wgt) {
-        tmpw.alloc(2 * std::max<int64_t>(P.no, 1));
-        HIPCHK(hipMemsetAsync(tmpw.p, 0, 2 * P.no * 8, c.stream));
-        if (c.nobs > 0)
-            c.launch<k_weight_rows>(dim3((unsigned)cdiv(c.nobs, 256)), dim3(256), 0, c.d, dev_unw, tmpw.p);
-    }
-    if (c.multi()) {
-        c.do_allreduce(dev_unw, 2 * P.no);
-        if (r_wgt) c.do_allreduce(tmpw.p, 2 * P.no);
-    }
-    const double *zfull = c.gathered(zdev);
-    std::vector<double> zh(P.NZ);
-    if (r_unw) HIPCHK(hipMemcpyAsync(r_unw, dev_unw, 2 * P.no * 8, hipMemcpyDeviceToHost, c.stream));
-    if (r_wgt) HIPCHK(hipMemcpyAsync(r_wgt, tmpw.p, 2 * P.no * 8, hipMemcpyDeviceToHost, c.stream));
-    HIPCHK(hipMemcpyAsync(zh.data(), zfull, P.NZ * 8, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-    int64_t row = 2 * P.no;
-    for (int64_t zi : P.prior_z) {
-        const double e = zh[zi] - P.z_prv[zi];
-        if (r_unw) r_unw[row] = e;
-        if (r_wgt) r_wgt[row] = e * std::sqrt(P.z_prw[zi]);
-        ++row;
-    }
-}
-}  // namespace dbat
-
-int dbat_hip_residual(dbat_hip_handle *h, const double *x, double *r_unweighted, double *f) {
-    API_TRY
-    if (!h || !x) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    DeviceGuard dev_guard(c.device);
-    c.x_to_z(x, c.zt.p);
-    export_residuals(c, c.zt.p, r_unweighted, nullptr, f);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_jacobian_blocks(dbat_hip_handle *h, const double *x, double *JEO, double *JOP, double *JIO) {
-    API_TRY
-    if (!h || !x) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    DeviceGuard dev_guard(c.device);
-    const Plan &P = c.P;
-    c.x_to_z(x, c.zt.p);
-    c.prep_cams(c.zt.p);
-    DevBuf<double> a, b, cc;
-    const int64_t no = std::max<int64_t>(P.no, 1);
-    if (JEO) { a.alloc(12 * no); HIPCHK(hipMemsetAsync(a.p, 0, 12 * no * 8, c.stream)); }
-    if (JOP) { b.alloc(6 * no); HIPCHK(hipMemsetAsync(b.p, 0, 6 * no * 8, c.stream)); }
-    if (JIO) { cc.alloc(2 * (int64_t)P.nIOrows * no); HIPCHK(hipMemsetAsync(cc.p, 0, 2 * (int64_t)P.nIOrows * no * 8, c.stream)); }
-    if (c.nobs > 0) c.jac_blocks(c.zt.p, a.p, b.p, cc.p);
-    if (JEO) HIPCHK(hipMemcpyAsync(JEO, a.p, 12 * P.no * 8, hipMemcpyDeviceToHost, c.stream));
-    if (JOP) HIPCHK(hipMemcpyAsync(JOP, b.p, 6 * P.no * 8, hipMemcpyDeviceToHost, c.stream));
-    if (JIO) HIPCHK(hipMemcpyAsync(JIO, cc.p, 2 * (int64_t)P.nIOrows * P.no * 8, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_jacobian_sample(dbat_hip_handle *h, const double *x, int64_t n, const int64_t *ip_col, double *res,
-                             double *JEO, double *JOP, double *JIO) {
-    API_TRY
-    if (!h || !x || n < 0 || (n > 0 && (!ip_col || !res || !JEO || !JOP || !JIO))) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    const Plan &P = c.P;
-    if (P.nranks > 1) { g_err = "dbat_hip_jacobian_sample: one-rank handles only"; return DBAT_HIP_EUNSUPPORTED; }
-    if (n == 0) return DBAT_HIP_OK;
-    // IP column -> position in processing order, for the requested columns only
-    std::vector<int64_t> pos((size_t)n, -1);
-    {
-        std::vector<std::pair<int64_t, int64_t>> want((size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-            if (ip_col[i] < 0 || ip_col[i] >= P.no) { g_err = "IP column out of range"; return DBAT_HIP_EINVAL; }
-            want[i] = {ip_col[i], i};
-        }
-        std::sort(want.begin(), want.end());
-        const int64_t nobs = (int64_t)P.o_row.size();
-        for (int64_t o = 0; o < nobs; ++o) {
-            auto it = std::lower_bound(want.begin(), want.end(), std::make_pair(P.o_row[o], (int64_t)-1));
-            for (; it != want.end() && it->first == P.o_row[o]; ++it) pos[it->second] = o;
-        }
-        // (a one-rank plan holds every IP column; the kernel indexes the observation arrays with these positions)
-        for (int64_t i = 0; i < n; ++i)
-            if (pos[i] < 0) { g_err = "dbat_hip_jacobian_sample: IP column " + std::to_string(ip_col[i]) + " is not in this handle's plan"; return DBAT_HIP_EINVAL; }
-    }
-    DeviceGuard dev_guard(c.device);
-    c.x_to_z(x, c.zt.p);
-    c.prep_cams(c.zt.p);
-    DevBuf<int64_t> dpos;
-    dpos.upload(pos);
-    const int R = P.nIOrows;
-    DevBuf<double> dr, a, b, cc;
-    dr.alloc(2 * n); a.alloc(12 * n); b.alloc(6 * n); cc.alloc(2 * (int64_t)R * n);
-    c.with_model([&](auto M) {
-        c.launch<k_jac_sample<M>>(dim3((unsigned)cdiv(n, 256)), dim3(256), 0, c.d, c.zt.p, c.cams.p, n, dpos.p, dr.p, a.p, b.p, cc.p);
-    });
-    HIPCHK(hipMemcpyAsync(res, dr.p, 2 * n * 8, hipMemcpyDeviceToHost, c.stream));
-    HIPCHK(hipMemcpyAsync(JEO, a.p, 12 * n * 8, hipMemcpyDeviceToHost, c.stream));
-    HIPCHK(hipMemcpyAsync(JOP, b.p, 6 * n * 8, hipMemcpyDeviceToHost, c.stream));
-    HIPCHK(hipMemcpyAsync(JIO, cc.p, 2 * (int64_t)R * n * 8, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_jacobian_csc(dbat_hip_handle *h, const double *x, int32_t weighted, int64_t *nnz_out,
-                          int64_t *colptr, int64_t *rowidx, double *val) {
-    API_TRY
-    if (!h || !x || !nnz_out) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    const Plan &P = c.P;
-    if (P.nranks > 1) { g_err = "dbat_hip_jacobian_csc: one-rank handles only"; return DBAT_HIP_EUNSUPPORTED; }
-    std::vector<int64_t> z2x((size_t)P.NZ, -1);
-    for (int64_t i = 0; i < P.n; ++i) z2x[P.x2z[i]] = i;
-    // columns of one observation: EO (6), IO (the camera's estimated IO columns), OP (3); -1 = no unknown
-    const int R = P.nIOrows;
-    auto cols_of = [&](int64_t o, int64_t *eo, int64_t *io, int *iorow, int &nio, int64_t *op) {
-        const int cam = P.o_cam[o];
-        for (int k = 0; k < 6; ++k) { const int32_t zc = P.cam_col[(size_t)cam * MAXCOL + k]; eo[k] = (P.cam_eo_est[cam] >> k) & 1u ? z2x[zc] : -1; }
-        nio = P.cam_ncol[cam] - 6;
-        for (int q = 0; q < nio; ++q) { io[q] = z2x[P.cam_col[(size_t)cam * MAXCOL + 6 + q]]; iorow[q] = P.cam_iorow[(size_t)cam * MAXIO + q]; }
-        for (int k = 0; k < 3; ++k) op[k] = z2x[P.NS + 3 * (int64_t)P.o_pt[o] + k];
-    };
-    const int64_t nobs = (int64_t)P.o_cam.size();
-    std::vector<int64_t> cnt((size_t)P.n + 1, 0);
-    int64_t eo[6], io[MAXIO], op[3];
-    int iorow[MAXIO], nio;
-    for (int64_t o = 0; o < nobs; ++o) {
-        cols_of(o, eo, io, iorow, nio, op);
-        for (int k = 0; k < 6; ++k) if (eo[k] >= 0) cnt[eo[k] + 1] += 2;
-        for (int q = 0; q < nio; ++q) if (io[q] >= 0) cnt[io[q] + 1] += 2;
-        for (int k = 0; k < 3; ++k) if (op[k] >= 0) cnt[op[k] + 1] += 2;
-    }
-    for (int64_t zi : P.prior_z) cnt[z2x[zi] + 1] += 1;
-    for (int64_t i = 0; i < P.n; ++i) cnt[i + 1] += cnt[i];
-    *nnz_out = cnt[P.n];
-    if (!colptr) return DBAT_HIP_OK;
-    if (!rowidx || !val) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    DeviceGuard dev_guard(c.device);
-    c.x_to_z(x, c.zt.p);
-    c.prep_cams(c.zt.p);
-    const int64_t no = std::max<int64_t>(P.no, 1);
-    DevBuf<double> a, b, cc;
-    a.alloc(12 * no); b.alloc(6 * no); cc.alloc(2 * (int64_t)R * no);
-    if (c.nobs > 0) c.jac_blocks(c.zt.p, a.p, b.p, cc.p);
-    std::vector<double> JEO((size_t)12 * no), JOP((size_t)6 * no), JIO((size_t)2 * R * no);
-    HIPCHK(hipMemcpyAsync(JEO.data(), a.p, JEO.size() * 8, hipMemcpyDeviceToHost, c.stream));
-    HIPCHK(hipMemcpyAsync(JOP.data(), b.p, JOP.size() * 8, hipMemcpyDeviceToHost, c.stream));
-    HIPCHK(hipMemcpyAsync(JIO.data(), cc.p, JIO.size() * 8, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-    for (int64_t i = 0; i <= P.n; ++i) colptr[i] = cnt[i];
-    std::vector<int64_t> fill(cnt.begin(), cnt.end() - 1);
-    // observations in REFERENCE row order (ascending IP column), so that the rows of a column ascend
-    std::vector<int64_t> by_row((size_t)nobs);
-    for (int64_t o = 0; o < nobs; ++o) by_row[P.o_row[o]] = o;
-    // reweighted observations (robust): the device's current weights, not the plan's
-    std::vector<double> ow_dev;
-    if (weighted && c.robust_on && nobs > 0) {
-        ow_dev.resize((size_t)2 * nobs);
-        HIPCHK(hipMemcpy(ow_dev.data(), c.o_w.p, ow_dev.size() * 8, hipMemcpyDeviceToHost));
-    }
-    const double *ow = ow_dev.empty() ? (P.uniform_w ? nullptr : P.o_w.data()) : ow_dev.data();
-    for (int64_t k = 0; k < nobs; ++k) {
-        const int64_t o = by_row[k];
-        const int cam = P.o_cam[o];
-        double w0 = 1.0, w1 = 1.0;
-        if (weighted) { w0 = ow ? ow[2 * o] : P.cam_w[2 * cam]; w1 = ow ? ow[2 * o + 1] : P.cam_w[2 * cam + 1]; }
-        cols_of(o, eo, io, iorow, nio, op);
-        auto put = [&](int64_t col, double v0, double v1) {
-            int64_t &f = fill[col];
-            rowidx[f] = 2 * k; val[f] = v0 * w0; rowidx[f + 1] = 2 * k + 1; val[f + 1] = v1 * w1;
-            f += 2;
-        };
-        for (int q = 0; q < 6; ++q) if (eo[q] >= 0) put(eo[q], JEO[12 * k + 2 * q], JEO[12 * k + 2 * q + 1]);
-        for (int q = 0; q < nio; ++q) if (io[q] >= 0) put(io[q], JIO[2 * (int64_t)R * k + 2 * iorow[q]], JIO[2 * (int64_t)R * k + 2 * iorow[q] + 1]);
-        for (int q = 0; q < 3; ++q) if (op[q] >= 0) put(op[q], JOP[6 * k + 2 * q], JOP[6 * k + 2 * q + 1]);
-    }
-    int64_t row = 2 * P.no;
-    for (int64_t zi : P.prior_z) {                       // prior rows: selection rows of I (prior_obs.m:45-72)
-        int64_t &f = fill[z2x[zi]];
-        rowidx[f] = row++; val[f] = weighted ? std::sqrt(P.z_prw[zi]) : 1.0;
-        ++f;
-    }
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
 int dbat_hip_linearize_solve(dbat_hip_handle *h, const double *x, double lambda, int32_t scale_columns,
                              double *p, double *stats) {
     API_TRY
@@ -2203,159 +1831,6 @@ int dbat_hip_linearize_solve(dbat_hip_handle *h, const double *x, double lambda,
     API_CATCH
 }
 
-int dbat_hip_gradient(dbat_hip_handle *h, double *g) {
-    API_TRY
-    if (!h || !g || !h->core->have_lin) { g_err = "no linearisation"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    DeviceGuard dev_guard(c.device);
-    c.ensure_build();                                 // (a linearisation the damping loop left to whoever needs it)
-    c.gradient(c.vtmp.p);
-    c.z_to_x(c.vtmp.p, g);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_colnorms(dbat_hip_handle *h, double *Jn) {
-    API_TRY
-    if (!h || !Jn || !h->core->have_lin) { g_err = "no linearisation"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    DeviceGuard dev_guard(c.device);
-    c.ensure_build();                                 // (a linearisation the damping loop left to whoever needs it)
-    c.colnorm2(c.vtmp.p);
-    c.z_to_x(c.vtmp.p, Jn);
-    for (int64_t i = 0; i < c.P.n; ++i) Jn[i] = std::sqrt(Jn[i]);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_jtimes_sqnorm(dbat_hip_handle *h, const double *v, double *sqnorm) {
-    API_TRY
-    if (!h || !v || !sqnorm || !h->core->have_lin) { g_err = "no linearisation"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    DeviceGuard dev_guard(c.device);
-    c.ensure_build();                                 // (a linearisation the damping loop left to whoever needs it)
-    HIPCHK(hipMemsetAsync(c.vtmp.p, 0, c.P.NZ * 8, c.stream));
-    if (c.P.n) {
-        HIPCHK(hipMemcpyAsync(c.xbuf.p, v, c.P.n * 8, hipMemcpyHostToDevice, c.stream));
-        c.launch<k_scatter_x>(dim3((unsigned)cdiv(c.P.n, 256)), dim3(256), 0, c.P.n, c.x2z.p, c.xbuf.p, c.vtmp.p);
-    }
-    double a, b, vv;
-    c.jtimes(c.vtmp.p, a, b, vv);
-    *sqnorm = a;
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-namespace dbat {
-// J v (v in z layout on the device) as host rows: image rows in the reference's order, then the prior rows -- at the
-// linearisation the handle holds (zlin)
-static void jtimes_rows(Core &c, const double *v_dev, double *Jv) {
-    const Plan &P = c.P;
-    if (!c.cams_at_lin) { c.prep_cams(c.zlin.p); c.cams_at_lin = true; }
-    DevBuf<double> out;
-    out.alloc(2 * std::max<int64_t>(P.no, 1));
-    if (c.nobs > 0) {
-        c.with_model([&](auto M) { with_value<6, 14, 15, MAXCOL>(c.tile_ncx, [&](auto NCX) {
-            c.launch<k_jtimes_vec<M, NCX>>(dim3((unsigned)cdiv(c.nobs, 256)), dim3(256), 0, c.d, c.zlin.p, c.cams.p, v_dev, out.p);
-        }); });
-    }
-    std::vector<double> vz(P.NZ);
-    HIPCHK(hipMemcpyAsync(Jv, out.p, 2 * P.no * 8, hipMemcpyDeviceToHost, c.stream));
-    HIPCHK(hipMemcpyAsync(vz.data(), v_dev, P.NZ * 8, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-    int64_t row = 2 * P.no;                                  // prior rows: selection rows of I, weighted (prior_obs.m:45-72)
-    for (int64_t zi : P.prior_z) Jv[row++] = vz[zi] * std::sqrt(P.z_prw[zi]);
-}
-}  // namespace dbat
-
-int dbat_hip_jtimes(dbat_hip_handle *h, const double *v, double *Jv) {
-    API_TRY
-    if (!h || !v || !Jv || !h->core->have_lin) { g_err = "no linearisation"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    const Plan &P = c.P;
-    if (P.nranks > 1) { g_err = "dbat_hip_jtimes: one-rank handles only"; return DBAT_HIP_EUNSUPPORTED; }
-    DeviceGuard dev_guard(c.device);
-    c.ensure_build();                                 // (a linearisation the damping loop left to whoever needs it)
-    HIPCHK(hipMemsetAsync(c.vtmp.p, 0, P.NZ * 8, c.stream));
-    if (P.n) {
-        HIPCHK(hipMemcpyAsync(c.xbuf.p, v, P.n * 8, hipMemcpyHostToDevice, c.stream));
-        c.launch<k_scatter_x>(dim3((unsigned)cdiv(P.n, 256)), dim3(256), 0, P.n, c.x2z.p, c.xbuf.p, c.vtmp.p);
-    }
-    jtimes_rows(c, c.vtmp.p, Jv);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-namespace dbat {
-static void solve_once(Core &c, const dbat_hip_options *opt, double *x, dbat_hip_result *result, double *res, double *damp,
-                       double *aux, double *trace) {
-    c.n_res_evals = c.n_lin = c.n_solves = c.n_trace_only = 0;
-    c.veto_stats_reset();
-    c.trace_begin();
-    c.x_to_z(x, c.z.p);
-    c.lambda_lin = NAN;
-    LoopOut out;
-    const auto t0 = std::chrono::steady_clock::now();
-    c.stages_begin();
-    struct StageGuard { Core &c; ~StageGuard() { c.st_on = false; } } stage_guard{c};     // (a loop that throws must not leave the timers on)
-    switch (opt->damping) {
-        case DBAT_HIP_DAMP_GM: loop_gm(c, *opt, out); break;
-        case DBAT_HIP_DAMP_GNA: loop_gna(c, *opt, out); break;
-        case DBAT_HIP_DAMP_LM: loop_lm(c, *opt, out); break;
-        default: {
-            double delta0 = opt->delta0;
-            if (!(delta0 > 0)) {                                   // bundle.m:325 delta0 = norm(x0)
-                double s = 0;
-                for (int64_t i = 0; i < c.P.n; ++i) s += x[i] * x[i];
-                delta0 = std::sqrt(s);
-            }
-            loop_lmp(c, *opt, delta0, out);
-        }
-    }
-    c.sync();
-    result->time_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    c.stages_end(result->stage_s);
-    result->code = out.code; result->iters = out.iters;
-    c.z_to_x(c.z.p, x);
-    const int cap_res = opt->max_iter + 3, cap_d = 2 * opt->max_iter + 4;
-    result->n_res = (int)std::min<size_t>(out.res.size(), cap_res);
-    if (res) for (int i = 0; i < result->n_res; ++i) res[i] = out.res[i];
-    result->n_damp = (int)std::min<size_t>(out.damp.size(), cap_d);
-    if (damp) for (int i = 0; i < result->n_damp; ++i) damp[i] = out.damp[i];
-    if (aux) for (int i = 0; i < cap_d; ++i) aux[i] = i < (int)out.aux.size() ? out.aux[i] : NAN;
-    result->n_trace = 0;
-    if (opt->store_trace && trace) {
-        const int cap_t = opt->max_iter + 2;
-        result->n_trace = c.trace_download(trace, cap_t);
-    }
-    const double dof = (double)(c.P.m - c.P.n);
-    result->sigma0 = std::sqrt(2 * out.f_final / dof);            // bundle.m:476-483
-    result->n_residual_evals = c.n_res_evals; result->n_linearizations = c.n_lin; result->n_solves = c.n_solves;
-    result->n_trace_only = c.n_trace_only;
-}
-
-static const char *solve_args_error(const dbat_hip_handle *h, const dbat_hip_options *opt, const double *x, const dbat_hip_result *result,
-                                    const double *trace, int &rc) {
-    rc = DBAT_HIP_EINVAL;
-    if (!h || !opt || !x || !result) return "null argument";
-    if (opt->damping < 0 || opt->damping > 3) return "Unknown damping";
-    if (opt->store_trace && !trace) return "store_trace without a trace buffer";
-    rc = DBAT_HIP_EUNSUPPORTED;
-    if (opt->term_fun && h->core->P.nranks > 1) return "term_fun: one-rank handles only (J*p rows stay with their shard)";
-    return nullptr;
-}
-
-static const char *robust_args_error(const dbat_hip_robust_options *ro) {
-    if (!ro) return "null argument";
-    if (ro->loss != DBAT_HIP_LOSS_HUBER && ro->loss != DBAT_HIP_LOSS_CAUCHY) return "robust: unknown loss";
-    if (!(ro->k > 0) || !std::isfinite(ro->k)) return "robust: k must be positive and finite";
-    if (ro->scale != DBAT_HIP_SCALE_APRIORI && ro->scale != DBAT_HIP_SCALE_MAD) return "robust: unknown scale";
-    if (ro->max_outer < 1 || ro->max_outer >= DBAT_HIP_ROBUST_MAX_OUTER) return "robust: max_outer out of range";
-    if (!(ro->weight_tol >= 0) || !std::isfinite(ro->weight_tol)) return "robust: weight_tol must be finite and >= 0";
-    return nullptr;
-}
-}  // namespace dbat
-
 int dbat_hip_solve(dbat_hip_handle *h, const dbat_hip_options *opt, double *x, dbat_hip_result *result,
                    double *res, double *damp, double *aux, double *trace) {
     API_TRY
@@ -2364,123 +1839,6 @@ int dbat_hip_solve(dbat_hip_handle *h, const dbat_hip_options *opt, double *x, d
     Core &c = *h->core;
     DeviceGuard dev_guard(c.device);
     solve_once(c, opt, x, result, res, damp, aux, trace);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_default_robust_options(int32_t loss, dbat_hip_robust_options *ropt) {
-    if (!ropt || (loss != DBAT_HIP_LOSS_HUBER && loss != DBAT_HIP_LOSS_CAUCHY)) { g_err = "bad loss"; return DBAT_HIP_EINVAL; }
-    ropt->loss = loss;
-    ropt->k = loss == DBAT_HIP_LOSS_HUBER ? 1.5 : 2.385;
-    ropt->scale = DBAT_HIP_SCALE_APRIORI;
-    ropt->max_outer = 10;
-    ropt->weight_tol = 1e-3;
-    return DBAT_HIP_OK;
-}
-
-int dbat_hip_robust_weights(dbat_hip_handle *h, const double *x, const dbat_hip_robust_options *ropt,
-                            double *omega, double *s_norm, double *scale) {
-    API_TRY
-    if (!h || !x || !omega) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    if (const char *e = robust_args_error(ropt)) { g_err = e; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    const Plan &P = c.P;
-    DeviceGuard dev_guard(c.device);
-    c.x_to_z(x, c.zt.p);
-    DevBuf<double> om, sn;
-    om.alloc((size_t)std::max<int64_t>(P.no, 1));
-    HIPCHK(hipMemsetAsync(om.p, 0, (size_t)P.no * sizeof(double), c.stream));
-    if (s_norm) {
-        sn.alloc((size_t)std::max<int64_t>(P.no, 1));
-        HIPCHK(hipMemsetAsync(sn.p, 0, (size_t)P.no * sizeof(double), c.stream));
-    }
-    double sc = 1.0, chg = 0.0;
-    c.robust_eval(c.zt.p, *ropt, sn.p, om.p, sc, chg);
-    if (c.multi()) {
-        c.do_allreduce(om.p, P.no);
-        if (s_norm) c.do_allreduce(sn.p, P.no);
-    }
-    HIPCHK(hipMemcpyAsync(omega, om.p, (size_t)P.no * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    if (s_norm) HIPCHK(hipMemcpyAsync(s_norm, sn.p, (size_t)P.no * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    HIPCHK(hipStreamSynchronize(c.stream));
-    if (scale) *scale = sc;
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_set_obs_weights(dbat_hip_handle *h, const double *omega) {
-    API_TRY
-    if (!h) { g_err = "null handle"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    const Plan &P = c.P;
-    DeviceGuard dev_guard(c.device);
-    if (!omega) { c.robust_reset(); return DBAT_HIP_OK; }
-    for (int64_t i = 0; i < P.no; ++i)
-        if (!(omega[i] > 0.0 && omega[i] <= 1.0)) {
-            g_err = "dbat_hip_set_obs_weights: omega[" + std::to_string(i) + "] is not in (0, 1]";
-            return DBAT_HIP_EINVAL;
-        }
-    c.robust_promote();
-    if (c.nobs > 0) {           // processing order of this rank's observations
-        std::vector<double> om((size_t)c.nobs);
-        for (int64_t k = 0; k < c.nobs; ++k) om[k] = omega[P.o_row[k]];
-        HIPCHK(hipMemcpy(c.omega.p, om.data(), om.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    c.robust_apply_omega();
-    HIPCHK(hipStreamSynchronize(c.stream));
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_solve_robust(dbat_hip_handle *h, const dbat_hip_options *opt, const dbat_hip_robust_options *ropt,
-                          double *x, dbat_hip_result *result, double *res, double *damp, double *aux, double *trace,
-                          dbat_hip_robust_result *rr, double *omega_out) {
-    API_TRY
-    int rc;
-    if (const char *e = solve_args_error(h, opt, x, result, trace, rc)) { g_err = e; return rc; }
-    if (!rr) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    if (const char *e = robust_args_error(ropt)) { g_err = e; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    if (c.chirality) { g_err = "robust solve: the chirality veto (dbat_hip_set_chirality) is not combined with the reweighting loop"; return DBAT_HIP_EUNSUPPORTED; }
-    DeviceGuard dev_guard(c.device);
-    memset(rr, 0, sizeof *rr);
-    auto t0 = std::chrono::steady_clock::now();
-    auto rw_clock = [&]() {
-        const auto now = std::chrono::steady_clock::now();
-        rr->reweight_s += std::chrono::duration<double>(now - t0).count();
-    };
-    c.robust_promote();
-    c.robust_set_ones();
-    HIPCHK(hipStreamSynchronize(c.stream));
-    rw_clock();
-    solve_once(c, opt, x, result, res, damp, aux, trace);
-    rr->inner_iters[0] = result->iters;
-    rr->outer = 1;
-    for (int t = 1; t <= ropt->max_outer && result->code == 0; ++t) {
-        t0 = std::chrono::steady_clock::now();
-        c.x_to_z(x, c.zt.p);
-        double sc = 1.0, chg = 0.0;
-        c.robust_eval(c.zt.p, *ropt, nullptr, nullptr, sc, chg);
-        rr->scale[t - 1] = sc;
-        rr->max_change = chg;
-        if (chg <= ropt->weight_tol) { rr->converged = 1; rw_clock(); break; }
-        c.robust_apply_eval(*ropt, sc);
-        HIPCHK(hipStreamSynchronize(c.stream));
-        rw_clock();
-        solve_once(c, opt, x, result, res, damp, aux, trace);
-        rr->inner_iters[rr->outer++] = result->iters;
-    }
-    if (omega_out) c.robust_omega_ip(omega_out);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_final_residuals(dbat_hip_handle *h, double *r_unweighted, double *r_weighted) {
-    API_TRY
-    if (!h || !h->core->have_lin) { g_err = "no linearisation"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    DeviceGuard dev_guard(c.device);
-    export_residuals(c, c.zlin.p, r_unweighted, r_weighted, nullptr);
     return DBAT_HIP_OK;
     API_CATCH
 }
@@ -2601,89 +1959,6 @@ int dbat_hip_bench_step(dbat_hip_handle *h, double lambda, int32_t scale_columns
     API_CATCH
 }
 
-int dbat_hip_posterior_cov(dbat_hip_handle *h, const double *x, double sigma0, double *CEO, double *CIO,
-                           double *COP, double *Sinv) {
-    API_TRY
-    if (!h || !x) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    DeviceGuard dev_guard(c.device);
-    c.x_to_z(x, c.z.p);
-    c.posterior_cov(sigma0, CEO, CIO, COP, Sinv);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_redundancy(dbat_hip_handle *h, const double *x, double *qvv_ip, double *r_prior) {
-    API_TRY
-    if (!h || !x || !qvv_ip || (!r_prior && !h->core->P.prior_z.empty())) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    DeviceGuard dev_guard(c.device);
-    c.x_to_z(x, c.z.p);
-    c.redundancy(qvv_ip, r_prior);
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_forwintersect(dbat_hip_handle *h, const double *x, const uint8_t *skip, double *OP) {
-    API_TRY
-    if (!h || !x || !OP) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Core &c = *h->core;
-    DeviceGuard dev_guard(c.device);
-    const Plan &P = c.P;
-    c.x_to_z(x, c.zt.p);                              // IO / EO of the rays
-    c.prep_cams(c.zt.p);
-    DevBuf<double> dOP;
-    dOP.alloc((size_t)3 * std::max(P.np, 1));
-    HIPCHK(hipMemsetAsync(dOP.p, 0, (size_t)3 * P.np * sizeof(double), c.stream));
-    if (c.nb > 0) c.launch<k_forwintersect>(dim3((unsigned)c.nb), dim3(P.BT), (size_t)P.BT * 9 * sizeof(double), c.d, c.cams.p, dOP.p);
-    if (c.ngiant > 0) c.launch<k_forwintersect_giant>(dim3((unsigned)c.ngiant), dim3(256), 0, c.d, c.cams.p, dOP.p);
-    if (c.multi()) c.do_allreduce(dOP.p, (int64_t)3 * P.np);             // every point is computed by its owner
-    std::vector<double> tmp((size_t)3 * P.np);
-    HIPCHK(hipMemcpyAsync(tmp.data(), dOP.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-    std::vector<uint8_t> seen((size_t)P.np, 0);       // points without any observation: NaN (pm_multiforwintersect.m:41)
-    for (int32_t r : P.o_pt) seen[r] = 1;
-    if (c.multi()) std::fill(seen.begin(), seen.end(), 1);               // (other shards' points arrive through the sum)
-    const double nan = std::nan("");
-    for (int64_t p = 0; p < P.np; ++p) {
-        if (skip && skip[p]) continue;                // keeps the caller's value (forwintersect.m:32-36)
-        const int64_t r = P.pt_rank[p];
-        for (int k = 0; k < 3; ++k) OP[3 * p + k] = seen[r] ? tmp[3 * r + k] : nan;
-    }
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-int dbat_hip_resect(int32_t device, int32_t n_images, const int64_t *pt_start, const double *X, const double *xn,
-                    const int64_t *tri_start, const int32_t *tri, double *P, double *rms) {
-    API_TRY
-    if (n_images < 0 || !pt_start || !tri_start || !P || !rms) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device: the dbat_hip core has no CPU path"; return DBAT_HIP_EDEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "bad device index"; return DBAT_HIP_EINVAL; }
-    if (n_images == 0) return DBAT_HIP_OK;
-    if (pt_start[0] != 0 || tri_start[0] != 0) { g_err = "ranges must start at 0"; return DBAT_HIP_EINVAL; }
-    for (int c = 0; c < n_images; ++c)
-        if (pt_start[c + 1] < pt_start[c] || tri_start[c + 1] < tri_start[c]) { g_err = "ranges must ascend"; return DBAT_HIP_EINVAL; }
-    const int64_t npt = pt_start[n_images], ntri = tri_start[n_images];
-    if ((npt > 0 && (!X || !xn)) || (ntri > 0 && !tri)) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    for (int c = 0; c < n_images; ++c)
-        for (int64_t t = 3 * tri_start[c]; t < 3 * tri_start[c + 1]; ++t)
-            if (tri[t] < 0 || tri[t] >= pt_start[c + 1] - pt_start[c]) { g_err = "triangle index outside the camera's points"; return DBAT_HIP_EINVAL; }
-    DeviceGuard dev_guard(device);
-    DevBuf<int64_t> dps, dts;
-    DevBuf<double> dX, dx, dP, dr;
-    DevBuf<int32_t> dtri;
-    dps.upload(pt_start, (size_t)n_images + 1); dts.upload(tri_start, (size_t)n_images + 1);
-    dX.upload(X, (size_t)3 * npt); dx.upload(xn, (size_t)2 * npt); dtri.upload(tri, (size_t)3 * ntri);
-    dP.alloc((size_t)12 * n_images); dr.alloc((size_t)n_images);
-    launch<k_resect>(dim3((unsigned)n_images), dim3(64), 0, (hipStream_t)nullptr, n_images, dps.p, dX.p, dx.p, dts.p, dtri.p, 1, dP.p, dr.p);
-    HIPCHK(hipMemcpy(P, dP.p, (size_t)12 * n_images * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(rms, dr.p, (size_t)n_images * sizeof(double), hipMemcpyDeviceToHost));
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
 int dbat_hip_chol_stats(const dbat_hip_handle *h, int64_t *st) {
     if (!h || !st) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
     const Core &c = *h->core;
@@ -2719,200 +1994,6 @@ int dbat_hip_info(const dbat_hip_handle *h, int64_t *info) {
         info[16] = c.P.hv_ntasks; info[17] = c.P.hv_mfma; info[18] = c.P.hv_ngroups; info[19] = c.P.hv_z_doubles * 8;
         info[20] = c.P.hv_npts; info[21] = c.nobs - c.P.hv_obs0; info[22] = c.P.hv_ks_per_task; info[23] = c.P.hv_alg_flops;
     }
-    return DBAT_HIP_OK;
-}
-
-
-/* Digest of the host plan (debug / CPU tests only: the plan must be identical bit for bit whatever the number of
- * threads that built it).  out[k] = FNV-1a hash of the k-th field of Plan in the order of plan_digest_names(). */
-#define DBAT_PLAN_FIELDS(X)                                                                                           \
-    X(x2z) X(io_src) X(io_fixed) X(z_est) X(z_prw) X(z_prv) X(z_mine) X(z0) X(prior_z) X(porder) X(pt_rank) X(o_cam)    \
-    X(o_pt) X(o_uv) X(o_w) X(o_seg) X(o_row) X(batch_start) X(o_lc) X(o_pidx) X(tile_batch) X(tile_cam_start)           \
-    X(tile_order) X(tile_cams) X(cm_pt) X(cm_uv) X(cm_w) X(cm_chunk_cam) X(cm_chunk_start) X(giant_start)               \
-    X(tile_io_start) X(tile_iocols) X(tile_cam_io) X(tile_io_simple) X(sg_chunk) X(sg_tile_chunk0) X(sg_lc) X(sg_gcam)  \
-    X(sg_uv) X(sg_w) X(cam_w) X(cam_ncol) X(cam_col) X(cam_iorow) X(cam_eo_est) X(px) X(cam_first) X(cam_adj)
-int dbat_hip_debug_plan_digest(const dbat_hip_problem *prob, uint64_t *out, int32_t n_out, char *names, int32_t names_len) {
-    API_TRY
-    if (!prob || !out) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Plan P;
-    if (!build_plan(*prob, P, true)) { g_err = P.err; return DBAT_HIP_EINVAL; }
-    auto fnv = [](const void *p, size_t n) {
-        uint64_t h = 1469598103934665603ull;
-        const unsigned char *b = (const unsigned char *)p;
-        for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
-        return h ^ (uint64_t)n;
-    };
-    std::vector<uint64_t> hs;
-    std::string nm;
-#define X(F) hs.push_back(fnv(P.F.data(), P.F.size() * sizeof(P.F[0]))); nm += #F ",";
-    DBAT_PLAN_FIELDS(X)
-#undef X
-    hs.push_back(fnv(P.nd.order.data(), P.nd.order.size() * sizeof(int))); nm += "nd.order,";
-    hs.push_back(fnv(P.nd.block_end.data(), P.nd.block_end.size() * sizeof(int))); nm += "nd.block_end,";
-    hs.push_back(fnv(P.nd.cam_owner.data(), P.nd.cam_owner.size() * sizeof(int))); nm += "nd.cam_owner,";
-    const int64_t sc[] = {P.n, P.m, P.NS, P.NZ, P.nIOu, P.pt_lo, P.pt_hi, P.CMAX, P.nb_tiled, P.n_cm_chunks_tiled, P.sg_kmax, P.sg_rows_max,
-                          P.sg_ngroups, P.sg_npoints, P.sg_ok, P.sg_backsub_ok, P.BT, P.ncolmax, P.with_io, P.uniform_w, P.all_std8, P.max_k,
-                          P.shared_eo, P.rank_ok, P.order_dims, P.mg_subtree, P.n_tiles_io_simple, P.n_prior[0], P.n_prior[1], P.n_prior[2]};
-    hs.push_back(fnv(sc, sizeof(sc))); nm += "scalars";
-    if ((int)hs.size() > n_out) { g_err = "digest buffer too small"; return DBAT_HIP_EINVAL; }
-    for (size_t i = 0; i < hs.size(); ++i) out[i] = hs[i];
-    for (int i = (int)hs.size(); i < n_out; ++i) out[i] = 0;
-    if (names && names_len > 0) snprintf(names, (size_t)names_len, "%s", nm.c_str());
-    return (int)hs.size();
-    API_CATCH
-}
-
-/* Host only (debug / CPU unit tests; never used by the product path): the index structures of the heavy / giant points
- * (Plan::hv_*, csrc/heavy.hpp) checked against their definition.  Every row of Z that k_heavy_z would write gets a
- * pseudo-random value (a hash of its point, its row of the reduced system and its k-column) at the place the plan gives
- * it; the tasks of k_heavy_syrk are then replayed on the host (same operand places, same flush rules) and compared with
- * the plain sum over the points of z_p z_p' over ALL their rows.  out[8]: { 1 if the plan takes the path, untiled points,
- * row groups, tasks, k-steps, largest absolute difference, largest absolute entry, number of compared entries }. */
-int dbat_hip_debug_heavy_plan_selftest(const dbat_hip_problem *prob, double *out) {
-    API_TRY
-    if (!prob || !out) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Plan P;
-    if (!build_plan(*prob, P, true)) { g_err = P.err; return DBAT_HIP_EINVAL; }
-    for (int i = 0; i < 8; ++i) out[i] = 0.0;
-    if (!P.hv_ok) return DBAT_HIP_OK;
-    const int64_t NS = P.NS;
-    if (NS > 4000) { g_err = "selftest: reduced system too large for the dense host check"; return DBAT_HIP_EINVAL; }
-    auto val = [](int64_t pt, int64_t row, int c) {
-        uint64_t h = (uint64_t)pt * 0x9E3779B97F4A7C15ull ^ (uint64_t)(row + 1) * 0xC2B2AE3D27D4EB4Full ^ (uint64_t)(c + 1) * 0x165667B19E3779F9ull;
-        h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 32;
-        return (double)(int64_t)(h % 2001) / 1000.0 - 1.0;
-    };
-    std::vector<double> Zs((size_t)P.hv_z_doubles, 0.0);
-    std::vector<double> ref((size_t)(NS + 1) * (NS + 1), 0.0), got((size_t)(NS + 1) * (NS + 1), 0.0);
-    const int64_t ho0 = P.hv_obs0, ho1 = (int64_t)P.o_cam.size();
-    // rows of every point: (row of the reduced system, values of the three k-columns)
-    std::vector<int64_t> prow; std::vector<double> pval;
-    int64_t o = ho0;
-    while (o < ho1) {
-        const int32_t pt = P.o_pt[o];
-        const int32_t hp = pt - P.hv_pt0;
-        prow.clear(); pval.clear();
-        std::vector<int32_t> slot_row((size_t)(P.hv_pt_io0[hp + 1] - P.hv_pt_io0[hp]), -1);
-        int64_t oe = o;
-        for (; oe < ho1 && P.o_pt[oe] == pt; ++oe) {
-            const int32_t c = P.o_cam[oe];
-            const int32_t dst = P.hv_obs_dst[oe - ho0];
-            const int ld = P.hv_obs_ld[oe - ho0];
-            for (int a = 0; a < 6; ++a) {
-                const int64_t row = P.cam_col[(size_t)c * MAXCOL + a];
-                prow.push_back(row);
-                for (int k = 0; k < 3; ++k) { const double v = val(pt, row, k); pval.push_back(v); Zs[(size_t)dst + (size_t)k * ld + a] = v; }
-            }
-            for (int q = 6; q < P.cam_ncol[c]; ++q) {
-                const int sl = P.hv_obs_ioloc[(size_t)(oe - ho0) * Plan::HV_NIOC + (q - 6)];
-                if (sl >= (int)slot_row.size()) { g_err = "selftest: IO slot out of range"; return DBAT_HIP_EINVAL; }
-                const int32_t row = P.cam_col[(size_t)c * MAXCOL + q];
-                if (slot_row[sl] >= 0 && slot_row[sl] != row) { g_err = "selftest: two IO columns in one slot"; return DBAT_HIP_EINVAL; }
-                slot_row[sl] = row;
-            }
-        }
-        for (size_t sl = 0; sl < slot_row.size(); ++sl) {
-            if (slot_row[sl] < 0) { g_err = "selftest: IO slot without a column"; return DBAT_HIP_EINVAL; }
-            const int gs = P.hv_pt_io0[hp] + (int)sl;
-            if (P.hv_io_pt[gs] != hp) { g_err = "selftest: IO slot of another point"; return DBAT_HIP_EINVAL; }
-            prow.push_back(slot_row[sl]);
-            for (int k = 0; k < 3; ++k) { const double v = val(pt, slot_row[sl], k); pval.push_back(v); Zs[(size_t)P.hv_io_dst[gs] + (size_t)k * P.hv_io_ld[gs]] = v; }
-        }
-        prow.push_back(NS);
-        for (int k = 0; k < 3; ++k) { const double v = val(pt, NS, k); pval.push_back(v); Zs[(size_t)P.hv_pt_y[2 * hp] + (size_t)k * P.hv_pt_y[2 * hp + 1]] = v; }
-        for (size_t a = 0; a < prow.size(); ++a)
-            for (size_t b = 0; b < prow.size(); ++b) {
-                const int64_t ri = prow[a], rj = prow[b];
-                if (ri < rj || (ri == NS && rj == NS)) continue;
-                ref[(size_t)rj * (NS + 1) + ri] -= pval[3 * a] * pval[3 * b] + pval[3 * a + 1] * pval[3 * b + 1] + pval[3 * a + 2] * pval[3 * b + 2];
-            }
-        o = oe;
-    }
-    // the tasks, as k_heavy_syrk runs them
-    int64_t nks_all = 0;
-    for (int t = 0; t < P.hv_ntasks; ++t) {
-        const int gi = P.hv_task[4 * t], gj = P.hv_task[4 * t + 1], ks0 = P.hv_task[4 * t + 2], nks = P.hv_task[4 * t + 3];
-        const int nbi = P.hv_grp_nb[gi], nbj = P.hv_grp_nb[gj];
-        nks_all += nks;
-        std::vector<double> acc((size_t)48 * 48, 0.0);
-        for (int ks = 0; ks < nks; ++ks)
-            for (int kk = 0; kk < 4; ++kk) {
-                const int32_t *op = P.hv_ops.data() + ((size_t)(ks0 + ks) * 4 + kk) * 2;
-                if ((op[0] < 0) != (op[1] < 0)) { g_err = "selftest: half an operand"; return DBAT_HIP_EINVAL; }
-                if (op[0] < 0) continue;
-                for (int i = 0; i < 16 * nbi; ++i)
-                    for (int j = 0; j < 16 * nbj; ++j) acc[(size_t)i * 48 + j] += Zs[(size_t)op[0] + i] * Zs[(size_t)op[1] + j];
-            }
-        for (int i = 0; i < 16 * nbi; ++i)
-            for (int j = 0; j < 16 * nbj; ++j) {
-                if (gi == gj && i < j) continue;
-                const int32_t ri = P.hv_grp_row[(size_t)gi * 48 + i], cj = P.hv_grp_row[(size_t)gj * 48 + j];
-                if (ri < 0 || cj < 0 || cj == NS) continue;
-                if (ri < cj) { g_err = "selftest: rows of the groups are not ascending"; return DBAT_HIP_EINVAL; }
-                got[(size_t)cj * (NS + 1) + ri] -= acc[(size_t)i * 48 + j];
-            }
-    }
-    double dmax = 0, vmax = 0; int64_t ncmp = 0;
-    for (size_t i = 0; i < ref.size(); ++i) {
-        dmax = std::max(dmax, std::fabs(ref[i] - got[i])); vmax = std::max(vmax, std::fabs(ref[i]));
-        ncmp += ref[i] != 0.0;
-    }
-    out[0] = 1; out[1] = P.hv_npts; out[2] = P.hv_ngroups; out[3] = P.hv_ntasks; out[4] = (double)nks_all;
-    out[5] = dmax; out[6] = vmax; out[7] = (double)ncmp;
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-/* Host only (debug / CPU unit tests): the sizes of the batches of the plan.  out[16]: for the tiled batches {most points
- * of one batch, most observations of one batch, batches closed by Plan::PMAX rather than by BT, most batches of one
- * tile}, the same four for the batches after the tiles (heavy points; every batch when nothing is tiled; the last
- * entry 0), then {BT, Plan::PMAX, the plan's cap of batches per tile, tiled batches, untiled batches}, zeros. */
-int dbat_hip_debug_batch_stats(const dbat_hip_problem *prob, int64_t *out) {
-    API_TRY
-    if (!prob || !out) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    Plan P;
-    if (!build_plan(*prob, P, true)) { g_err = P.err; return DBAT_HIP_EINVAL; }
-    for (int i = 0; i < 16; ++i) out[i] = 0;
-    const int64_t nb = (int64_t)P.batch_start.size() - 1;
-    for (int64_t b = 0; b < nb; ++b) {
-        const int64_t o0 = P.batch_start[b], o1 = P.batch_start[b + 1];
-        if (o1 <= o0) continue;
-        int64_t *st = out + (b < P.nb_tiled ? 0 : 4);
-        st[0] = std::max<int64_t>(st[0], (int64_t)P.o_pidx[o1 - 1] + 1);
-        st[1] = std::max<int64_t>(st[1], o1 - o0);
-    }
-    out[2] = P.nb_pcap[0]; out[6] = P.nb_pcap[1];
-    for (size_t t = 0; P.nb_tiled > 0 && t + 1 < P.tile_batch.size(); ++t)
-        out[3] = std::max<int64_t>(out[3], P.tile_batch[t + 1] - P.tile_batch[t]);
-    out[8] = P.BT; out[9] = Plan::PMAX; out[10] = P.tile_bmax; out[11] = P.nb_tiled; out[12] = nb - P.nb_tiled;
-    return DBAT_HIP_OK;
-    API_CATCH
-}
-
-/* Host evaluation of the per-observation model (debug / CPU unit tests of
- * model.hpp only; never used by the product path). */
-int dbat_hip_debug_model_eval_host(int32_t model, int32_t nK, int32_t nP, const double *EO6, const double *IO,
-                                   double px_size, const double *Q3, const double *uv, double *r2,
-                                   double *A12, double *B6, double *C /* 2 x nIOrows */) {
-    if (model < 2 || model > 5 || nK < 0 || nK > MAXK || nP < 0 || nP > MAXP) { g_err = "bad model"; return DBAT_HIP_EINVAL; }
-    CamRec c{};
-    c.c[0] = EO6[0]; c.c[1] = EO6[1]; c.c[2] = EO6[2];
-    cam_rotation(EO6 + 3, c.Mt, c.sk, c.ck);
-    c.f = IO[0]; c.pp[0] = IO[1]; c.pp[1] = IO[2]; c.b[0] = IO[3]; c.b[1] = IO[4];
-    for (int k = 0; k < nK; ++k) c.K[k] = IO[5 + k];
-    for (int k = 0; k < nP; ++k) c.P[k] = IO[5 + nK + k];
-    c.sz = px_size;
-    double r[2], A[2][6], B[2][3], Cf[2][MAXIO];
-    switch (model) {
-        case 2: obs_eval<2, true, true>(c, nK, nP, Q3, uv[0], uv[1], r, A, B, Cf); break;
-        case 3: obs_eval<3, true, true>(c, nK, nP, Q3, uv[0], uv[1], r, A, B, Cf); break;
-        case 4: obs_eval<4, true, true>(c, nK, nP, Q3, uv[0], uv[1], r, A, B, Cf); break;
-        default: obs_eval<5, true, true>(c, nK, nP, Q3, uv[0], uv[1], r, A, B, Cf); break;
-    }
-    r2[0] = r[0]; r2[1] = r[1];
-    for (int k = 0; k < 6; ++k) { A12[2 * k] = A[0][k]; A12[2 * k + 1] = A[1][k]; }
-    for (int k = 0; k < 3; ++k) { B6[2 * k] = B[0][k]; B6[2 * k + 1] = B[1][k]; }
-    for (int k = 0; k < 5 + nK + nP; ++k) { C[2 * k] = Cf[0][k]; C[2 * k + 1] = Cf[1][k]; }
     return DBAT_HIP_OK;
 }
 

@@ -1,5 +1,5 @@
-// Host side of the point depths and the chirality veto at zt (kernels: depth.hpp), included by dbat_core.hip after Core
-// and analysis_host.hpp.  The state (Core::dep, the veto's switch and counters) stays with Core: the loops consult it.
+// Host side of the point depths and the chirality veto at zt (kernels: depth.hpp), included by dbat_core.hip after Core,
+// analysis_host.hpp and robust_host.hpp (cm_slots).  The state (Core::dep, the veto's switch and counters) stays with Core: the loops consult it.
 #pragma once
 
 namespace dbat {
@@ -13,7 +13,7 @@ static void depth_plan(Core &c) {
     if (dep.ready) return;
     const Plan &P = c.P;
     std::vector<int64_t> col((size_t)std::max<int64_t>(c.nobs, 1), 0);
-    const std::vector<int32_t> cmm = c.cm_slots();
+    const std::vector<int32_t> cmm = cm_slots(c);        // (robust_host.hpp)
     for (int64_t o = 0; o < c.nobs; ++o) col[(size_t)cmm[o]] = P.o_row[o];
     dep.cm_col.upload(col);
     dep.chunk_col.alloc((size_t)std::max<int64_t>(c.n_cm_chunks_all, 1));
