@@ -117,6 +117,10 @@ class RobustOptions(C.Structure):
     ]
 
 
+class PairOptions(C.Structure):           # dbat_hip_pair_options
+    _fields_ = [('max_iter', C.c_int32), ('conv_tol', C.c_double), ('min_angle', C.c_double)]
+
+
 class RobustResult(C.Structure):
     _fields_ = [
         ('outer', C.c_int32), ('converged', C.c_int32), ('inner_iters', C.c_int32 * ROBUST_MAX_OUTER),
@@ -177,6 +181,9 @@ SYMBOLS = {
     'dbat_hip_essmat5': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, _dp, _ip]),
     'dbat_hip_relorient': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, C.POINTER(C.c_int64), _ip, _dp,
                                      C.c_int32, _dp, _dp, _ip, _bp, _bp, _dp]),
+    'dbat_hip_default_pair_options': (C.c_int, [C.POINTER(PairOptions)]),
+    'dbat_hip_pairadjust': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, _bp, _dp, _dp, C.c_int32,
+                                      C.POINTER(PairOptions), _dp, _dp, _bp, _dp, _ip, _dp, _dp]),
     'dbat_hip_bench_step': (C.c_int, [_H, C.c_double, C.c_int32, _dp]),
     'dbat_hip_structure_key': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_uint64)]),
     'dbat_hip_handle_key': (C.c_int, [_H, C.POINTER(C.c_uint64)]),
@@ -216,6 +223,8 @@ DEBUG_SYMBOLS = {
     'dbat_hip_debug_align_timing': (C.c_int, [C.c_int32]),
     'dbat_hip_debug_relorient_ms': (C.c_int, [_dp]),
     'dbat_hip_debug_relorient_timing': (C.c_int, [C.c_int32]),
+    'dbat_hip_debug_pairadjust_ms': (C.c_int, [_dp]),
+    'dbat_hip_debug_pairadjust_timing': (C.c_int, [C.c_int32]),
 }
 
 _lib = None
@@ -976,6 +985,58 @@ def relorient_ms():
     ms = np.zeros(3)
     check(load().dbat_hip_debug_relorient_ms(dptr(ms)))
     return dict(solve=float(ms[0]), score=float(ms[1]), cams=float(ms[2]))
+
+
+PAIR_CODES = ('converged', 'max_iter', 'no_step', 'singular', 'too_few')
+
+
+def pairadjust(pt_start, x1, x2, P2, X, use=None, w1=None, w2=None, front_dir=-1, max_iter=20, conv_tol=1e-6, min_angle=0.0,
+               residuals=False, device=0):
+    """dbat_hip_pairadjust over the pairs pt_start[i] .. pt_start[i + 1] of the columns of x1, x2 (2-by-total), from the
+    start values P2 (n, 3, 4: [R | t]) and X (3-by-total); use (total booleans) and the weights w1, w2 (2-by-total, or
+    anything that broadcasts to it) are optional, min_angle is in radians.  Nothing given is changed.  Returns
+    dict(P2 (n, 3, 4), X (3, total), used (total), f0, f, sigma0, lam (n), code, iters, trials, n_used (n), Q (n, 6, 6),
+    res (2, 2, total: image, axis; None unless residuals))."""
+    lib = load()
+    ps = np.ascontiguousarray(pt_start, np.int64)
+    n = len(ps) - 1
+    x1, x2, X = np.asarray(x1, float), np.asarray(x2, float), np.asarray(X, float)
+    P2 = np.asarray(P2, float).reshape(-1, 3, 4)
+    if n < 0 or x1.ndim != 2 or x1.shape[0] != 2 or x1.shape != x2.shape or x1.shape[1] != ps[-1] or X.shape != (3, x1.shape[1]) \
+            or P2.shape[0] != n:
+        raise ValueError('pairadjust: x1 and x2 must be 2-by-total, X 3-by-total, total the end of the last range, and P2 one 3-by-4 per pair')
+    total = x1.shape[1]
+    a, b = _f64(x1), _f64(x2)
+    wt = [None if w is None else _f64(np.broadcast_to(np.asarray(w, float), (2, total))) for w in (w1, w2)]
+    u = None if use is None else np.ascontiguousarray(np.broadcast_to(np.asarray(use, bool), (total,))).view(np.uint8)
+    P = np.ascontiguousarray(P2.transpose(0, 2, 1)).reshape(-1).copy()
+    P = np.concatenate([P, np.zeros(12)]) if n == 0 else P
+    Xf = X.flatten('F')
+    Xf = np.zeros(3) if total == 0 else Xf
+    used, ds, ist, Q = np.zeros(max(total, 1), np.uint8), np.zeros(4 * max(n, 1)), np.zeros(4 * max(n, 1), np.int32), np.zeros(36 * max(n, 1))
+    res = np.zeros(4 * max(total, 1)) if residuals else None
+    opt = PairOptions(int(max_iter), float(conv_tol), float(min_angle))
+    check(lib.dbat_hip_pairadjust(int(device), n, ps.ctypes.data_as(C.POINTER(C.c_int64)), dptr(a), dptr(b),
+                                  None if u is None else u.ctypes.data_as(_bp), dptr(wt[0]), dptr(wt[1]), int(front_dir), C.byref(opt),
+                                  dptr(P), dptr(Xf), used.ctypes.data_as(_bp), dptr(ds), ist.ctypes.data_as(_ip), dptr(Q), dptr(res)))
+    ds, ist = ds[:4 * n].reshape(n, 4), ist[:4 * n].reshape(n, 4)
+    return dict(P2=P[:12 * n].reshape(n, 4, 3).transpose(0, 2, 1), X=Xf[:3 * total].reshape(3, total, order='F'), used=used[:total].astype(bool),
+                f0=ds[:, 0].copy(), f=ds[:, 1].copy(), sigma0=ds[:, 2].copy(), lam=ds[:, 3].copy(), code=ist[:, 0].copy(),
+                iters=ist[:, 1].copy(), trials=ist[:, 2].copy(), n_used=ist[:, 3].copy(), Q=Q[:36 * n].reshape(n, 6, 6).transpose(0, 2, 1),
+                res=None if res is None else res[:4 * total].reshape(total, 2, 2).transpose(1, 2, 0))
+
+
+def pairadjust_timing(on=True):
+    """Device events around the kernel of pairadjust calls on this thread (debug; off by default)."""
+    check(load().dbat_hip_debug_pairadjust_timing(int(bool(on))))
+
+
+def pairadjust_ms():
+    """Device-event milliseconds of the kernel of the last pairadjust call on this thread, after pairadjust_timing(True)
+    (debug)."""
+    ms = np.zeros(1)
+    check(load().dbat_hip_debug_pairadjust_ms(dptr(ms)))
+    return float(ms[0])
 
 
 def rigidalign(X, Y, scale=False, use=None, resid=False, device=0):

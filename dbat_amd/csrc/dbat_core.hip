@@ -32,6 +32,7 @@
 #include "quality.hpp"
 #include "align.hpp"
 #include "relorient.hpp"
+#include "pairadjust.hpp"
 
 namespace dbat {
 
@@ -2001,3 +2002,4 @@ int dbat_hip_info(const dbat_hip_handle *h, int64_t *info) {
 
 #include "align_host.hpp"         // the network transforms take no handle
 #include "relorient_host.hpp"     // nor does the relative orientation
+#include "pairadjust_host.hpp"    // nor its least-squares refinement

@@ -10,6 +10,9 @@ control points and forward intersection of the object points, on
   camsfrome, relorient, relorient_pairs -> dbat_hip_relorient (k_essmat5, k_ro_score, k_ro_cams): relative orientation
                    of image pairs without control points or EO -- a five-point RANSAC over samples drawn here, the
                    camera pair and the points of the winner                (photogrammetry/camsfrome.m:16-59)
+  refine_pairs, relorient(refine=True) -> dbat_hip_pairadjust (csrc/pairadjust.hpp k_pairadjust): the least-squares
+                   relative orientation of the pairs, one workgroup per pair; the reference refines a pair only through
+                   bundle.m on a two-image project
   largesttriangle (misc/largesttriangle.m:16-41), derotmat3d (photogrammetry/derotmat3d.m:17-19), rotmat3d (its inverse),
   lenscorr1 (bundle/cammodel/pm_multilenscorr1.m:45-69 + pm_lens1.m:36-72), cleareo, clearop (misc/)
 
@@ -292,7 +295,77 @@ def relorient_pairs(s, pairs, n_hyp=512, thr_px=3.0, seed=0, device=0):
     return out
 
 
-def relorient(s0, i, j, n_hyp=512, thr_px=3.0, seed=0, device=0):
+def pair_weights(s, i, j):
+    """(w1, w2), 2-by-n each: the reciprocal standard deviations of the image points of pair_points(s, i, j) in its
+    normalised units, |f_c| / (pxSize[axis, c] IP.std[axis, column]), with one pixel size for both axes where the sensor
+    says samePxSize (as lenscorr1 takes it)."""
+    ri, rj = np.flatnonzero(s.IP.cam == i), np.flatnonzero(s.IP.cam == j)
+    _, ai, aj = np.intersect1d(s.IP.pt[ri], s.IP.pt[rj], return_indices=True)
+    out = []
+    for cam, rows in ((i, ri[ai]), (j, rj[aj])):
+        px = np.asarray(s.IO.sensor.pxSize, float)[:, cam]
+        if getattr(s.IO.sensor, 'samePxSize', False):
+            px = np.array([px[0], px[0]])
+        out.append(abs(s.IO.val[0, cam]) / (px[:, None] * np.asarray(s.IP.std, float)[:, rows]))
+    return out[0], out[1]
+
+
+def refine_pairs(s, pairs, infos, max_iter=20, conv_tol=1e-6, min_angle_deg=0.0, device=0):
+    """Least-squares refinement of the relative orientations infos = relorient_pairs(s, pairs, ...): per pair a two-view
+    bundle adjustment over R, t (|t| = 1, image i at the origin) and the points, all pairs with info['ok'] in one device
+    call (dbat_hip_pairadjust; include/dbat_hip.h has the algorithm); s is not touched.  The correspondences that are
+    inliers and in front may be used, with the weights of pair_weights.  min_angle_deg leaves out the correspondences
+    whose two rays meet at less: such a point is not determined along its ray, and under the iteration it runs towards
+    infinity and keeps the pair from converging.  It is off by default -- which angle is too small depends on the
+    noise, and no value has been measured on real projects; a pair without a baseline is not repaired by it and ends
+    with a code other than 0.  Returns a list of dict per pair with
+      P2, X (3-by-n), used       as relorient_pairs; X of a point that is not used is the given one
+      sigma0, f0, f              sqrt(f / (n_used - 5)), the weighted sum of squares at the start and at the end
+      iters, trials, code, ok    accepted steps, trials, 0 converged / 1 max_iter / 2 no step / 3 singular / 4 fewer than
+                                 five points or not info['ok'] (nothing is refined: P2 and X are those of info); ok: code 0
+      Q, cov                     6-by-6 cofactor and covariance sigma0^2 Q of the rotation vector a (R <- exp([a]x) R) and t
+      res                        2-by-2-by-n weighted residuals (image, axis), zero where not used
+    The lens correction is applied to the measurements (lenscorr1), not to the projections: with distortion the
+    objective is that of bundle() to first order only."""
+    from . import _hip
+    pairs, infos = list(pairs), list(infos)
+    if len(pairs) != len(infos):
+        raise ValueError('refine_pairs: one info per pair')
+    nan = np.nan
+    out = [dict(P2=np.array(f['P2'], float), X=np.array(f['X'], float), used=np.zeros(f['X'].shape[1], bool), sigma0=nan, f0=nan, f=nan,
+                iters=0, trials=0, code=4, ok=False, Q=np.full((6, 6), nan), cov=np.full((6, 6), nan), res=np.zeros((2, 2, f['X'].shape[1])))
+           for f in infos]
+    todo = [k for k, f in enumerate(infos) if f['ok']]
+    if not todo:
+        return out
+    xy = lenscorr1(s)
+    pt_start, x1s, x2s, w1s, w2s = [0], [], [], [], []
+    for k in todo:
+        i, j = int(pairs[k][0]), int(pairs[k][1])
+        common, a, b = pair_points(s, i, j, xy)
+        if not np.array_equal(common, infos[k]['pts']):
+            raise ValueError('refine_pairs: info %d is not that of the pair (%d, %d) of s' % (k, i, j))
+        w1, w2 = pair_weights(s, i, j)
+        x1s.append(a); x2s.append(b); w1s.append(w1); w2s.append(w2)
+        pt_start.append(pt_start[-1] + common.size)
+    X0 = np.concatenate([infos[k]['X'] for k in todo], 1)
+    use = np.concatenate([infos[k]['inlier'] & infos[k]['in_front'] for k in todo])
+    r = _hip.pairadjust(pt_start, np.concatenate(x1s, 1), np.concatenate(x2s, 1), np.stack([infos[k]['P2'] for k in todo]),
+                        np.where(use, X0, 0.0), use=use, w1=np.concatenate(w1s, 1), w2=np.concatenate(w2s, 1), front_dir=-1,
+                        max_iter=max_iter, conv_tol=conv_tol, min_angle=np.deg2rad(min_angle_deg), residuals=True, device=device)
+    for m, k in enumerate(todo):
+        sl = slice(pt_start[m], pt_start[m + 1])
+        used = r['used'][sl].copy()
+        s0 = float(r['sigma0'][m])
+        out[k] = dict(P2=r['P2'][m].copy(), X=np.where(used, r['X'][:, sl], infos[k]['X']), used=used, sigma0=s0, f0=float(r['f0'][m]),
+                      f=float(r['f'][m]), iters=int(r['iters'][m]), trials=int(r['trials'][m]), code=int(r['code'][m]),
+                      ok=bool(r['code'][m] == 0), Q=r['Q'][m].copy(), cov=s0 * s0 * r['Q'][m], res=r['res'][:, :, sl].copy())
+        if out[k]['code'] == 4:
+            out[k]['P2'] = np.array(infos[k]['P2'], float)
+    return out
+
+
+def relorient(s0, i, j, n_hyp=512, thr_px=3.0, seed=0, device=0, refine=False, max_iter=20, conv_tol=1e-6, min_angle_deg=0.0):
     """Initial values for the image pair (i, j) of a network without control points or EO: (s, ok, info).  info is that
     of relorient_pairs(s0, [(i, j)], ...).  In s -- a copy -- the EO of image i is the origin with zero angles, the EO of
     image j comes from P2 = [R | t] (centre -R' t, a baseline of length one; omega, phi, kappa of R, as resect() takes
@@ -300,19 +373,29 @@ def relorient(s0, i, j, n_hyp=512, thr_px=3.0, seed=0, device=0):
     (the frame is new: no other point has coordinates in it; forwintersect() fills them once more images are oriented).
     The EO of the other images are left as they are.  ok = False, and s is s0 itself, when no sample gave a model or the
     best of the four camera candidates does not have strictly more points in front than the next (sp[0] > sp[1]): a
-    pair without a baseline, for one."""
+    pair without a baseline, for one.
+    refine: the winner is refined by least squares (refine_pairs with max_iter, conv_tol, min_angle_deg) and
+    info['refined'] is its result.  Where that ends with code 0, the EO of image j and the OP of the points it used come
+    from the refined values (a point in front that it did not use keeps its intersection); with any other code the
+    unrefined values stand and info['refined']['code'] says why."""
     from .dbatstruct import copy_struct
     info = relorient_pairs(s0, [(i, j)], n_hyp=n_hyp, thr_px=thr_px, seed=seed, device=device)[0]
     if not info['ok']:
         return s0, False, info
+    P2, X = info['P2'], info['X']
+    if refine:
+        ref = refine_pairs(s0, [(i, j)], [info], max_iter=max_iter, conv_tol=conv_tol, min_angle_deg=min_angle_deg, device=device)[0]
+        info['refined'] = ref
+        if ref['ok']:
+            P2, X = ref['P2'], ref['X']
     s = copy_struct(s0)
-    R, t = info['P2'][:, :3], info['P2'][:, 3]
+    R, t = P2[:, :3], P2[:, 3]
     s.EO.val[:6, i] = 0.0
     s.EO.val[:3, j] = -R.T @ t
     s.EO.val[3:6, j] = derotmat3d(R)
     s.OP.val[:] = np.nan
     f = info['in_front']
-    s.OP.val[:, info['pts'][f]] = info['X'][:, f]
+    s.OP.val[:, info['pts'][f]] = X[:, f]
     return s, True, info
 
 

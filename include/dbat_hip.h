@@ -498,6 +498,69 @@ int  dbat_hip_relorient(int32_t device, int32_t n_pairs, const int64_t *pt_start
                         const int64_t *hyp_start, const int32_t *samples, const double *thr2, int32_t front_dir,
                         double *E, double *P2, int32_t *stats, uint8_t *inlier, uint8_t *in_front, double *X);
 
+/* ---- least-squares relative orientation (additive to ABI 5; csrc/pairadjust.hpp) -------- */
+
+typedef struct dbat_hip_pair_options {
+    int32_t max_iter;           /* 1 .. 200 accepted steps at most */
+    double  conv_tol;           /* > 0: stop when q <= conv_tol^2 f (below) */
+    double  min_angle;          /* radians, [0, pi/2): correspondences whose two rays meet at less are not used */
+} dbat_hip_pair_options;
+
+/* max_iter = 20, conv_tol = 1e-6, min_angle = 0 (no correspondence is left out for its angle). */
+int  dbat_hip_default_pair_options(dbat_hip_pair_options *opt);
+
+/* Least-squares refinement of the relative orientation of n_pairs image pairs in one call: per pair a two-view bundle
+ * adjustment in the gauge of camsfrome (photogrammetry/camsfrome.m:16-33: camera 1 is [I | 0], camera 2 [R | t] with
+ * |t| = 1) over R, t and the points that pm_forwintersect3.m:55-82 intersects once and camsfrome.m:59 returns.  No
+ * handle, no plan; one workgroup per pair runs the whole damped loop.  The reference has no counterpart: it refines a
+ * pair only through bundle.m on a two-image project with a datum chosen by the caller (one camera fixed and one
+ * baseline coordinate), which has the same optimum up to the scale of the model.
+ *   pt_start  [n_pairs+1]  range of every pair's correspondences; a pair may be empty
+ *   x1, x2    [2*total]    as dbat_hip_relorient
+ *   use       [total]      or NULL (all): correspondences that may be used
+ *   w1, w2    [2*total]    or NULL (ones): weights per coordinate, the reciprocal standard deviations in normalised units
+ *   front_dir              +1 / -1: the sign of z in front of the cameras
+ *   P2        [12*n_pairs] in/out: [R | t], column-major 3 x 4; t of any length but zero comes to unit length
+ *   X         [3*total]    in/out: the points in the frame of camera 1; those not used keep their bits
+ *   used      [total]      out: the correspondences used, chosen once at the start orientation: use is set, the point
+ *                          is in front of both cameras (front_dir z > 0 in both frames), and the rays (x1, 1) and
+ *                          R' (x2, 1) satisfy |d1 x d2|^2 >= sin^2(min_angle) |d1|^2 |d2|^2.  A point near the epipole
+ *                          is not determined along its ray and runs away under the iteration, taking the pair with it
+ *   dstat     [4*n_pairs]  out: the objective at the start, the objective, sigma0, lambda
+ *   istat     [4*n_pairs]  out: code, iterations (accepted steps), trials, n (the correspondences used)
+ *   Q         [36*n_pairs] out: cofactor matrix, 6 x 6 of rank five, of the rotation vector a (R <- exp([a]x) R) and the
+ *                          change of t: blkdiag(I, B) inv(S0) blkdiag(I, B)' with S0 the undamped reduced matrix at the
+ *                          returned values and B a basis of the plane across t; in these coordinates it does not depend
+ *                          on B.  The covariance is sigma0^2 Q
+ *   res       [4*total]    out, or NULL: weighted residuals at the returned values, image 1 x, y, image 2 x, y; zero for
+ *                          correspondences not used
+ * Residuals: w1 (pi(X) - x1) and w2 (pi(R X + t) - x2), pi(Y) = Y(1:2) / Y(3); f is the sum of their squares.  A step is
+ * R <- exp([a]x) R, t <- (t + B b) / |t + B b|, X <- X + d: five unknowns and three per point.  Levenberg-Marquardt with
+ * Marquardt's scaling (lambda diag V added to every 3 x 3 point block, lambda diag U to the 5 x 5 pose block), the
+ * points eliminated.  lambda starts at 1e-3.  A trial is accepted if its objective is finite and smaller and every used
+ * point is in front of both cameras; then lambda <- max(lambda / 10, 1e-12).  Otherwise lambda <- 10 lambda and the same
+ * linearisation is solved again.  Every trial tests for the end first, with q = -g' delta the decrease its damped
+ * model predicts: q <= conv_tol^2 f, or f <= 1e-24 * 4 n (a noise-free pair never meets the first).
+ * The normal equations are float64.  The objective of the accept test is not: near the optimum a step's decrease is
+ * below the rounding of a float64 evaluation, and an accept test that answers at random stops the iteration short.  The
+ * residuals are formed and summed as pairs of doubles, and R is such a pair kept orthonormal to 1e-31 (its rounding
+ * across the rotations would move f as well); the returned f and R are the high words.
+ * Codes: 0 converged; 1 max_iter steps done; 2 no acceptable step before lambda > 1e8; 3 converged, but some V_k has a
+ * Cholesky pivot <= 1e-12 of its diagonal entry or S0 one <= 1e-10: Q is NaN; 4 fewer than five correspondences used:
+ * P2 and X are returned as given, dstat is NaN but for lambda.  Every other code returns the last accepted values.
+ * sigma0 = sqrt(f / (n - 5)), NaN for n = 5.  Q is NaN for every singular end, whatever the code.  Nothing else
+ * returned is ever non-finite.  The sums have a fixed shape and there are no atomics: two calls give the same bits, and
+ * a pair gives the same bits alone and in a batch.
+ * DBAT_HIP_EINVAL, before any device call: a coordinate, weight, P2 or point to be used (use) that is not finite; a
+ * weight <= 0; front_dir not +-1; an R with |R'R - I| > 1e-6 or det R < 0; t = 0; max_iter outside 1 .. 200;
+ * conv_tol <= 0; min_angle outside [0, pi/2); a pt_start that does not ascend from 0.  Then DBAT_HIP_EDEVICE without a
+ * HIP device (no CPU path).  What the data of one pair cause -- too few points, no convergence, singularity -- is that
+ * pair's code, never an error. */
+int  dbat_hip_pairadjust(int32_t device, int32_t n_pairs, const int64_t *pt_start, const double *x1, const double *x2,
+                         const uint8_t *use, const double *w1, const double *w2, int32_t front_dir,
+                         const dbat_hip_pair_options *opt, double *P2, double *X, uint8_t *used, double *dstat,
+                         int32_t *istat, double *Q, double *res);
+
 /* ---- measurement hooks -------------------------------------------------- */
 
 /* One benchmark step = one Levenberg-Marquardt iteration's device work at
