@@ -812,9 +812,11 @@ struct Core {
     // are LDS atomics from several waves.
     int det_ncx() const { return P.ncolmax <= 6 ? 6 : (P.ncolmax <= 14 ? 14 : 15); }
     bool deterministic_supported() const { return P.nranks == 1 && !P.shared_eo && P.ncolmax <= 15 && n_cm_chunks_all > 0; }
+    static constexpr const char *DET_CONDITION =
+        "deterministic mode: one rank, no shared EO blocks (camera stations), at most nine estimated IO columns per camera";
     void set_deterministic(bool on) {
         if (on && !deterministic_supported())
-            throw UsageError{"deterministic mode: one rank, no shared EO blocks (camera stations), at most nine estimated IO columns per camera"};
+            throw UsageError{DET_CONDITION};
         if (on && !det_u.p) {
             const int nc = P.nc;
             det_cam_part.alloc((size_t)std::max<int64_t>(n_cm_chunks_all, 1) * DET_CP);
@@ -1849,7 +1851,7 @@ int dbat_hip_set_deterministic(dbat_hip_handle *h, int32_t on) {
     if (!h) { g_err = "null handle"; return DBAT_HIP_EINVAL; }
     Core &c = *h->core;
     if (on && !c.deterministic_supported()) {
-        g_err = "deterministic mode covers the signature-group path on one rank (no heavy or giant points, no irregular-visibility tile kernels)";
+        g_err = Core::DET_CONDITION;
         return DBAT_HIP_EUNSUPPORTED;
     }
     DeviceGuard dev_guard(c.device);

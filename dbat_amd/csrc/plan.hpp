@@ -142,6 +142,7 @@ struct Plan {
                                                    // every shared element is ONE unknown in the slot of its leading
                                                    // entry (cam_col), the other entries' slots are inert
     bool rank_ok = true;                           // structural rank test
+    bool tang_zero = false;                        // some camera estimates P3.. at P1 = P2 = 0 (tang_scale_zero): the rank test saw that
     // Heavy and giant points on the matrix cores (heavy.hpp).  The rows of the reduced system that these points touch
     // -- the EO rows of their cameras, the IO columns those cameras estimate, and one row for the right-hand side --
     // are cut into ROW GROUPS of at most 48 rows (eight cameras; three 16-row blocks of v_mfma_f64_16x16x4_f64).  A
@@ -486,11 +487,34 @@ inline void structure_key(const dbat_hip_problem &pb, uint64_t key[2]) {
     key[0] = h0; key[1] = h1;
 }
 
+// P3 and beyond scale the displacement of P1 and P2 (brown_tang.m:58-70).  In a camera whose P1 = P2 = 0 their entries of J
+// are exact zeros, which the reference's sparse J does not store: sprank(J) at x0 (gauss_newton_armijo.m:132-142) does
+// not count them.  True if camera c is such a camera (io_src / lead_io: the plan's serial indices of the IO entries).
+inline bool tang_scale_zero(const dbat_hip_problem &pb, int nK, const int32_t *io_src, const int64_t *lead_io, int c) {
+    const int R = 5 + pb.nK + pb.nP;
+    if (pb.nP <= 2) return false;
+    for (int r = 5 + nK; r < 5 + nK + 2; ++r) {
+        const int32_t s = io_src[(size_t)c * R + r];
+        if ((s >= 0 ? pb.IO_val[lead_io[s]] : pb.IO_val[(size_t)c * R + r]) != 0) return false;
+    }
+    return true;
+}
+inline bool any_estimated_tang_scale_zero(const dbat_hip_problem &pb, int nc, int nK, const int32_t *io_src, const int64_t *lead_io) {
+    const int R = 5 + pb.nK + pb.nP;
+    if (pb.nP <= 2) return false;
+    for (int c = 0; c < nc; ++c)
+        if (io_src[(size_t)c * R + 5 + nK + 2] >= 0 && tang_scale_zero(pb, nK, io_src, lead_io, c)) return true;
+    return false;
+}
+
 // New parameter values and prior observations for a plan of the same structure: z0, the fixed IO values, the prior
 // weights and values -- exactly what build_plan derives from IO_val, EO_val, OP_val and prior_*_val / prior_*_std.
 inline bool plan_set_values(const dbat_hip_problem &pb, Plan &P) {
     const int nc = P.nc, np = P.np, R = P.nIOrows;
     const Par par{Par::default_threads()};
+    // (the one place where the structural rank test looks at values)
+    if (any_estimated_tang_scale_zero(pb, nc, P.nK, P.io_src.data(), P.lead_io.data()) != P.tang_zero)
+        return fail(P, "P3.. estimated and P1 = P2 = 0 became non-zero or the reverse: the structural rank differs, create a new handle");
     for (size_t e = 0; e < (size_t)6 * nc; ++e) P.z0[e] = pb.EO_val[e];
     for (int k = 0; k < P.nIOu; ++k) P.z0[6 * (int64_t)nc + k] = pb.IO_val[P.lead_io[k]];
     par.run(np, [&](int64_t plo, int64_t phi, int) {
@@ -738,8 +762,11 @@ inline bool build_plan(const dbat_hip_problem &pb, Plan &P, bool with_obs) {
     }
     {
         std::vector<int64_t> rows(P.nIOu, 0);
-        for (int c = 0; c < nc; ++c)
-            for (int r = 0; r < R; ++r) { const int32_t s = distIO[(size_t)c * R + r]; if (s >= 0) rows[s] += 2 * (int64_t)n_cam[c]; }
+        P.tang_zero = any_estimated_tang_scale_zero(pb, nc, P.nK, distIO.data(), leadIO.data());
+        for (int c = 0; c < nc; ++c) {
+            const int rz = P.tang_zero && tang_scale_zero(pb, P.nK, distIO.data(), leadIO.data(), c) ? 5 + P.nK + 2 : R;   // rows from rz on: exact zeros
+            for (int r = 0; r < rz; ++r) { const int32_t s = distIO[(size_t)c * R + r]; if (s >= 0) rows[s] += 2 * (int64_t)n_cam[c]; }
+        }
         for (int k = 0; k < P.nIOu && P.rank_ok; ++k)
             if (rows[k] == 0 && !(P.z_prw[6 * (int64_t)nc + k] > 0)) P.rank_ok = false;
     }

@@ -800,3 +800,91 @@ def lm_count_is_stable(s, ito, margin=1e-9):
     five row permutations and 16 under the sixth (its last accepted step lowers ||r|| by 2e-14 relative)."""
     n, m, t = lm_decision_margins(s)
     return n == ito and m > margin and t > 1.0 + 1e-3
+
+
+# ---------------------------------------------------------------- interior-orientation patterns (tests/test_io_patterns_*.py)
+_STD8 = (0, 1, 2, 5, 6, 7, 8, 9)        # cc px py K1 K2 K3 P1 P2 at nK = 3, nP = 2
+_ONE, _HALF = 'one', 'half'             # block of camera c: 1 | 1 for c < nc // 2, else 2 | an int k: c % k + 1
+
+# name: (nK, nP, block rule, {block: estimated rows}, rows that take the block rule (None: all; the others block 1))
+IO_PATTERNS = {
+    'fixed-k0p0': (0, 0, _ONE, {}, None),
+    'fixed-k5p5': (5, 5, _ONE, {}, None),
+    'cc-only': (3, 2, _ONE, {1: (0,)}, None),
+    'as-sk-only': (3, 2, _ONE, {1: (3, 4)}, None),
+    'k0p0-cc-pp': (0, 0, _ONE, {1: (0, 1, 2)}, None),
+    'k4p0-radial': (4, 0, _ONE, {1: (0, 5, 6, 7, 8)}, None),
+    'all10': (3, 2, _ONE, {1: tuple(range(10))}, None),
+    'k5p2-11cols': (5, 2, _ONE, {1: (0, 1, 2, 3, 5, 6, 7, 8, 9, 10, 11)}, None),
+    'k5p2-all12': (5, 2, _ONE, {1: tuple(range(12))}, None),
+    'half-fixed-half-std8': (3, 2, _HALF, {2: _STD8}, None),
+    'half-cc-half-std8': (3, 2, _HALF, {1: (0,), 2: _STD8}, None),
+    'half-std8-half-9': (3, 2, _HALF, {1: _STD8, 2: _STD8 + (3,)}, None),
+    '2x-std8-interleaved': (3, 2, 2, {1: _STD8, 2: _STD8}, None),
+    '2x-9-interleaved': (3, 2, 2, {1: _STD8 + (3,), 2: _STD8 + (3,)}, None),
+    '3x-std8-interleaved': (3, 2, 3, {1: _STD8, 2: _STD8, 3: _STD8}, None),
+    'cc-shared-K-per-group': (3, 2, _HALF, {1: _STD8, 2: _STD8}, (5, 6, 7)),
+}
+
+# (pattern, IO rows with a prior observation, IO prior rows of the adjustment: leading, estimated entries only)
+IO_PRIOR_CASES = (('2x-9-interleaved', (0, 1, 2), 6), ('half-cc-half-std8', (0, 5), 3), ('all10', (3, 4), 2),
+                  ('cc-shared-K-per-group', (0, 5, 6, 7), 7))
+
+
+def io_pattern_struct(name, pattern, priors=None):
+    """The synth scene `name` ('tiny', 'small') rebuilt through dbatstruct.make_struct with the interior-orientation
+    set-up `pattern` of IO_PATTERNS: lens model (nK, nP), IO blocks and estimated IO rows (rows: 0 cc, 1 px, 2 py, 3 as,
+    4 sk, 5.. K1..KnK, then P1..PnP); datum by dependency on camera 0.  The only place that knows the patterns.
+
+    Values: the scene's cc, pp, K1-K3 and P1-P2 where the rows exist; as = 2e-3 and sk = -1e-3 everywhere, as start or as
+    fixed values (the image points were made with as = sk = 0: a few pixels of misfit at x0, nothing the adjustment
+    cannot absorb or leave in the residuals).  Further K start at 0.  'fixed-k5p5' gives K4, K5 and P3-P5 values at
+    which each term moves a point in the image corner (r = 21.6 mm) by about a pixel: K4 = px / r^9, K5 = px / r^11, and --
+    the tangential terms past P2 multiply the P1, P2 displacement, which is zero in the scene -- P1 = P2 = px / (3 r^2)
+    with P3 = r^-2, P4 = r^-4, P5 = r^-6.  All of these, and cc, differ from camera to camera by the factor
+    1 + 0.01 c / nc: the fixed values of a camera are its own, not its block's.
+
+    priors: IO rows that get a prior observation -- use = True for EVERY camera (also where the entry is fixed or not
+    the leading one of its block: the adjustment has to mask those), val = IO (1 + 1e-3) + 1e-4, std = |IO| 1e-2 + 1e-3.
+    Returns (s, truth)."""
+    from dbat_amd import synth
+    from dbat_amd.dbatstruct import make_struct, seteoest_depend
+    nK, nP, rule, est_rows, rows = IO_PATTERNS[pattern]
+    base, truth = synth.make_scene(name)
+    nc = base.EO.val.shape[1]
+    nrow = 5 + nK + nP
+    IO = np.zeros((nrow, nc))
+    IO[0:3] = base.IO.val[0:3]
+    IO[3], IO[4] = 2e-3, -1e-3
+    IO[5:5 + min(nK, 3)] = base.IO.val[5:5 + min(nK, 3)]
+    IO[5 + nK:5 + nK + min(nP, 2)] = base.IO.val[8:8 + min(nP, 2)]
+    px = float(np.ravel(base.IO.sensor.pxSize)[0])
+    if pattern == 'fixed-k5p5':
+        r2 = 18.0 ** 2 + 12.0 ** 2
+        percam = 1 + 0.01 * np.arange(nc) / nc
+        IO[0] *= percam
+        IO[8] = px / r2 ** 4.5 * percam
+        IO[9] = -px / r2 ** 5.5 * percam
+        IO[10] = px / (3 * r2) * percam
+        IO[11] = -px / (3 * r2) * percam
+        IO[12] = 1 / r2 * percam
+        IO[13] = -1 / r2 ** 2 * percam
+        IO[14] = 1 / r2 ** 3 * percam
+    cam = np.arange(nc)
+    group = np.ones(nc, int) if rule == _ONE else (1 + (cam >= nc // 2) if rule == _HALF else cam % rule + 1)
+    block = np.ones((nrow, nc), np.int32)
+    block[list(range(nrow)) if rows is None else list(rows)] = group[None, :]
+    est = np.zeros((nrow, nc), bool)
+    for g, rr in est_rows.items():
+        est[np.ix_(list(rr), np.flatnonzero(group == g))] = True
+    prior = None
+    if priors:
+        pr = list(priors)
+        use, val, std = np.zeros((nrow, nc), bool), np.full((nrow, nc), np.nan), np.full((nrow, nc), np.nan)
+        use[pr], val[pr], std[pr] = True, IO[pr] * (1 + 1e-3) + 1e-4, np.abs(IO[pr]) * 1e-2 + 1e-3
+        prior = (use, val, std)
+    s = make_struct(IO, base.EO.val, base.OP.val, base.IP.val, base.IP.cam, base.IP.pt, px, ip_std=base.IP.std,
+                    distModel=3, nK=nK, nP=nP, estIO=est, IOblock=block, priorIO=prior)
+    s = seteoest_depend(s, 0)
+    s.damping = base.damping
+    return s, truth
