@@ -213,6 +213,7 @@ DEBUG_SYMBOLS = {
     'dbat_hip_debug_plan_digest': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_uint64), C.c_int32, C.c_char_p, C.c_int32]),
     'dbat_hip_debug_heavy_plan_selftest': (C.c_int, [C.POINTER(Problem), _dp]),
     'dbat_hip_debug_batch_stats': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_int64)]),
+    'dbat_hip_debug_nd_stats': (C.c_int, [C.POINTER(Problem), C.c_int32, _dp]),
     'dbat_hip_debug_model_eval_host': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_double,
                                                  _dp, _dp, _dp, _dp, _dp, _dp]),
     'dbat_hip_debug_ray_angles_ms': (C.c_int, [_H, _dp, C.POINTER(C.c_int64)]),
@@ -1127,6 +1128,23 @@ def heavy_plan_selftest(s, shard_rank=0, shard_count=1):
     check(lib.dbat_hip_debug_heavy_plan_selftest(C.byref(p), dptr(out)))
     return dict(on=bool(out[0]), points=int(out[1]), row_groups=int(out[2]), tasks=int(out[3]), ksteps=int(out[4]),
                 max_diff=float(out[5]), max_abs=float(out[6]), entries=int(out[7]))
+
+
+def nd_stats(s, mode, shard_rank=0, shard_count=1):
+    """Host-only (debug): the nested dissection of the camera graph with the separators of `mode` (csrc/nd.hpp: 0 lower
+    boundary at the median, 1 minimum vertex cover at the median, 2 minimum cover with slid cuts) and with the ones the
+    model of the factorisation chooses, laid out in tiles and scored on the CPU (dbat_hip_debug_nd_stats).  Returns
+    (requested, chosen): cameras, blocks, tile_columns, tiles, chain (longest dependent chain of tile columns), products,
+    model_us, mode, valid (the independent check of the order: a permutation, no co-visible pair across a cut), run,
+    model ('list schedule' or 'estimate')."""
+    lib = load()
+    p, keep = problem_from_struct(s, 0, shard_rank, shard_count)
+    out = np.zeros(24)
+    check(lib.dbat_hip_debug_nd_stats(C.byref(p), int(mode), dptr(out)))
+    part = lambda v: dict(cameras=int(v[0]), blocks=int(v[1]), tile_columns=int(v[2]), tiles=int(v[3]), chain=int(v[4]),
+                          products=int(v[5]), model_us=float(v[6]), mode=int(v[7]), valid=int(v[8]) == 0, run=int(v[9]),
+                          model='estimate' if v[10] else 'list schedule')
+    return part(out[:12]), part(out[12:])
 
 
 def batch_stats(s, shard_rank=0, shard_count=1):

@@ -1367,7 +1367,7 @@ struct DataflowChol {
     // rank whose domain a tile column belongs to, -1 = top separator / IO): PHASE 1 = the columns of this rank's
     // domain and its share of every top tile (mode 4); PHASE 2 = the top columns, products over top columns only.
     struct JobList { std::vector<DfJob> jobs; std::vector<int> dptr, dep, own, sumjob, presum, bits, par; };
-    void build_jobs(int phase, const std::vector<uint64_t> &rowbits, const std::vector<int> &col_owner, int rank, JobList &L) {
+    void build_jobs(int phase, const std::vector<uint64_t> &rowbits, const std::vector<int> &col_owner, int rank, JobList &L, int merge_depth = 0) {
         auto has = [&](int i, int k) { return (rowbits[(size_t)i * W + (k >> 6)] >> (k & 63)) & 1ull; };
         const int split_min = std::max(env_int("DBAT_HIP_DF_SPLIT", 96), 2);
         const int chunk = std::max(env_int("DBAT_HIP_DF_CHUNK", 32), 1);
@@ -1383,16 +1383,56 @@ struct DataflowChol {
         const bool chain = use_chain && merge;
         auto inphase = [&](int c) { return c < nT && (phase == 0 || (phase == 1 ? col_owner[c] == rank : col_owner[c] < 0)); };
         std::vector<int> js;
+        // Where two parts of the dissection meet (the column that follows one part's last column and is the parent of the
+        // other's): a sum takes its products in column order and waits for each, so the products with one part's late
+        // columns would hold back everything behind them -- and both parts end late when they are alike.  merge_depth > 0:
+        // the sums of such a column and of the merge_depth - 1 columns after it are cut at the ends of the other part's
+        // last run: pieces whose inputs exist early go to helpers (DfJob), the owner keeps the run's own columns.
+        const int merge_min = 4;                                // ... where the owner keeps that many products
+        int merge_k = 0;
+        int run0 = 0;                                           // first column of the run that column k continues
+        std::vector<int> run_of(nT, 0), merge_cut;              // per column: first column of its run; cuts of a merge column's sums
         for (int k = 0; k < nT; ++k) {
+            if (chain && merge_depth > 0) {
+                if (!(k > 0 && (L.bits[k - 1] & 2))) { run0 = k; merge_cut.clear(); }
+                run_of[k] = run0;
+                int c = run0 - 1;
+                while (c >= 0 && L.par[c] != k) --c;            // the last column of the other part that ends in column k
+                if (c >= 0) { merge_cut.assign({run_of[c], c + 1, run0}); merge_k = k; }
+                else if (k - merge_k >= merge_depth) merge_cut.clear();
+            }
             // emit the job(s) of tile (i,k) with the products js; returns the owner job
             auto emit = [&](int i, int mode, int par, int jhi_owner) {
-                n_products += (long long)js.size();
-                const int nj = (int)js.size();
-                const int nch = nj > split_min ? (nj + chunk - 1) / chunk : 1;
                 auto push_products = [&](int q0, int q1) {
                     for (int q = q0; q < q1; ++q) { L.dep.push_back(L.own[(size_t)k * nT + js[q]]); L.dep.push_back(i != k ? L.own[(size_t)i * nT + js[q]] : -1); }
                     L.dptr.push_back((int)L.dep.size());
                 };
+                n_products += (long long)js.size();
+                const int nj = (int)js.size();
+                const int nch = nj > split_min ? (nj + chunk - 1) / chunk : 1;
+                // A column where two parts of the dissection meet: the products with the columns of the part that is NOT
+                // this column's own run are a helper's, so that the ones of the run -- the last to exist -- are not queued
+                // behind them (a sum takes its products in column order, and the other part ends when it ends).
+                if (nch == 1 && !merge_cut.empty()) {
+                    int qc[4], npc = 0, q0 = 0;                 // pieces [q0, qc[0]), [qc[0], qc[1]) ...: the non-empty ones before the run's
+                    for (int c : merge_cut) {
+                        const int q = (int)(std::lower_bound(js.begin(), js.end(), c) - js.begin());
+                        if (q > q0) { qc[npc++] = q; q0 = q; }
+                    }
+                    if (npc > 0 && nj - q0 >= merge_min) {
+                        q0 = 0;
+                        for (int c = 0; c < npc; ++c) {
+                            L.jobs.push_back(DfJob{i, k, js[q0], qc[c] < nj ? js[qc[c]] : jhi_owner, nparts + c, -1, 0, -1});
+                            push_products(q0, qc[c]);
+                            q0 = qc[c];
+                        }
+                        const int me = (int)L.jobs.size();
+                        L.jobs.push_back(DfJob{i, k, q0 < nj ? js[q0] : jhi_owner, jhi_owner, nparts, npc, mode, i == k ? par : -1});
+                        push_products(q0, nj);
+                        nparts += npc;
+                        return me;
+                    }
+                }
                 for (int c = 0; c + 1 < nch; ++c) {             // helpers
                     L.jobs.push_back(DfJob{i, k, js[chunk * c], js[chunk * (c + 1)], nparts + c, -1, 0, -1});
                     push_products(chunk * c, chunk * (c + 1));
@@ -1547,6 +1587,7 @@ struct DataflowChol {
         std::vector<double> key(nt), tcs(ncand);
         const int forced = env_int("DBAT_HIP_DF_ORDER", -1);
         for (int c = 0; c < ncand; ++c) {
+            if (quiet && forced < 0 && c != 0 && c != 3) { tcs[c] = 1e300; continue; }     // an order that is only scored: two of the keys
             if (c + 1 < ncand) for (int t = 0; t < nt; ++t) key[t] = est[t] - betas[c] * blev[t];
             else for (int t = 0; t < nt; ++t) key[t] = est[t] - c_prod * nprod_of(t);
             std::vector<int> ord = kahn(key);
@@ -1556,7 +1597,7 @@ struct DataflowChol {
         double cp = 0.0;
         for (int t = 0; t < nt; ++t) cp = std::max(cp, fin[t]);
         sim_critical_us.push_back(cp); sim_schedule_us.push_back(tbest);
-        if (env_on("DBAT_HIP_PLAN_STATS")) {
+        if (stats_on()) {
             fprintf(stderr, "[chol %s] %d tasks, critical path %.0f us; simulated with %d workgroups, key = earliest start - beta x bottom level:",
                     what, nt, cp, workers);
             for (int c = 0; c + 1 < ncand; ++c) fprintf(stderr, " beta %g: %.0f us,", betas[c], tcs[c]);
@@ -1567,10 +1608,11 @@ struct DataflowChol {
         for (int t = 0; t < nt; ++t) sorted[t] = jobs[best_ord[t]];
         jobs.swap(sorted);
     }
-    // common part: nz[i] = bitset of columns k <= i with a structurally non-zero tile (i, k), i = 0..nT
-    // (row nT = right-hand side, all columns), fill included.  col_owner (empty: one rank): see build_jobs.
-    bool finish_setup(const std::vector<uint64_t> &rowbits, const std::vector<int64_t> &toff,
-                      const std::vector<int> &col_owner = std::vector<int>(), int rank = 0) {
+    // Host half of the schedule: task lists, chain role, tables of the backward substitution.  No device call.
+    struct Sched { std::vector<int> colsA, colsB, bitsA, bitsB, par, pos, bkl, bptr, bidx; std::vector<uint64_t> rowbits_top; };
+    bool quiet = false;                                 // an order that is only scored (nd_select, nd.hpp): no statistics lines, two of the candidate task orders
+    bool stats_on() const { return !quiet && env_on("DBAT_HIP_PLAN_STATS"); }
+    void schedule_host(const std::vector<uint64_t> &rowbits, const std::vector<int> &col_owner, int rank, Sched &H) {
         auto has = [&](int i, int k) { return (rowbits[(size_t)i * W + (k >> 6)] >> (k & 63)) & 1ull; };
         if (const char *g = env_get("DBAT_HIP_DF_GRID")) grid = std::min(std::max(atoi(g), 1), 4096);
         nparts = 0; n_products = 0;
@@ -1602,7 +1644,7 @@ struct DataflowChol {
             }
             const double t_products = (double)nprod * 2.6 / std::min(grid, 256), t_chain = longest * 17.0;
             use_chain = t_products < 0.6 * t_chain;
-            if (env_on("DBAT_HIP_PLAN_STATS"))
+            if (stats_on())
                 fprintf(stderr, "[chol] %lld tile products (%.0f us over the workgroups), longest chain %d links (%.0f us): chain role %s\n",
                         nprod, t_products, longest, t_chain, use_chain ? "on" : "off");
         }
@@ -1619,14 +1661,30 @@ struct DataflowChol {
             for (int k : cols) runs += !(bits[k] & 1);
             return std::max(1, std::min(runs, env_int("DBAT_HIP_DF_CHAIN_WG", 32)));
         };
-        std::vector<int> colsA, colsB;
+        std::vector<int> &colsA = H.colsA, &colsB = H.colsB;
         sim_critical_us.clear(); sim_schedule_us.clear();
         JobList L;
-        std::vector<int> bkl;                                   // panels of the backward substitution, in task order
-        std::vector<uint64_t> rowbits_top;
+        std::vector<int> &bkl = H.bkl;                          // panels of the backward substitution, in task order
+        bkl.clear(); h_tasksB.clear(); ntasksB = 0; nchain = nchainB = 0; chain_wg = chain_wgB = 0;
         if (!two_phase) {
             build_jobs(0, rowbits, col_owner, rank, L);
             order_jobs(L, "all");
+            const int force_merge = env_int("DBAT_HIP_DF_MERGE", -1);
+            if (use_chain && force_merge != 0) {
+                // ... and the same with the sums cut where two parts of the dissection meet (build_jobs): kept where the
+                // simulated schedule is shorter by more than 1 % and the partial sums stay within 128 MB
+                // (DBAT_HIP_DF_MERGE=0 / 1: never / wherever the chain role is on)
+                const int np0 = nparts;
+                const long long prod0 = n_products;
+                JobList M;
+                nparts = 0; n_products = 0;
+                build_jobs(0, rowbits, col_owner, rank, M, 2);
+                order_jobs(M, "all, sums cut at the merge columns");
+                const bool better = nparts <= 4096 && (force_merge == 1 || sim_schedule_us[1] < 0.99 * sim_schedule_us[0]);
+                if (better) std::swap(L, M); else { nparts = np0; n_products = prod0; }
+                sim_critical_us.erase(sim_critical_us.begin() + (better ? 0 : 1)); sim_schedule_us.erase(sim_schedule_us.begin() + (better ? 0 : 1));
+                if (stats_on()) fprintf(stderr, "[chol] sums cut at the merge columns: %s (%d partial sums)\n", better ? "yes" : "no", nparts);
+            }
             split_chain(L, h_tasks, colsA); ntasks = (int)h_tasks.size();
             for (int j = nT - 1; j >= 0; --j) bkl.push_back(j);
         } else {
@@ -1637,29 +1695,27 @@ struct DataflowChol {
             build_jobs(2, rowbits, col_owner, rank, B);
             order_jobs(B, "top");
             split_chain(B, h_tasksB, colsB); ntasksB = (int)h_tasksB.size();
-            if (!up(d_tasksB, h_tasksB)) return false;
             if (use_chain) {
                 for (int k = 0; k < nT; ++k) if (B.par[k] >= 0) L.par[k] = B.par[k];      // (one table: a column is in one of the two lists)
                 nchainB = (int)colsB.size(); chain_wgB = chain_width(colsB, B.bits);
-                if (!up(d_chain_colsB, colsB) || !up(d_chain_bitsB, B.bits)) return false;
+                H.bitsB = B.bits;
             }
             // the top columns first (every rank), then this rank's domain: a dependency always has a smaller number
             for (int j = nT - 1; j >= 0; --j) if (col_owner[j] < 0) bkl.push_back(j);
             for (int j = nT - 1; j >= 0; --j) if (col_owner[j] == rank) bkl.push_back(j);
-            rowbits_top = rowbits;                              // the products of the second launch: top columns only
+            H.rowbits_top = rowbits;                            // the products of the second launch: top columns only
             for (int i = 0; i <= nT; ++i)
                 for (int k = 0; k < nT; ++k)
-                    if (col_owner[k] >= 0) rowbits_top[(size_t)i * W + (k >> 6)] &= ~(1ull << (k & 63));
-            if (!up(d_rowbits_top, rowbits_top)) return false;
+                    if (col_owner[k] >= 0) H.rowbits_top[(size_t)i * W + (k >> 6)] &= ~(1ull << (k & 63));
         }
         nbk = (int)bkl.size();
         if (use_chain) {
             nchain = (int)colsA.size(); chain_wg = chain_width(colsA, L.bits);
-            std::vector<int> pos(nT, 0);                          // (one table: a column is in one of the two lists)
-            for (size_t q = 0; q < colsA.size(); ++q) pos[colsA[q]] = (int)q;
-            for (size_t q = 0; q < colsB.size(); ++q) pos[colsB[q]] = (int)q;
-            if (!up(d_chain_cols, colsA) || !up(d_chain_bits, L.bits) || !up(d_chain_par, L.par) || !up(d_chain_pos, pos)) return false;
-            if (env_on("DBAT_HIP_PLAN_STATS")) {
+            H.pos.assign(nT, 0);                                  // (one table: a column is in one of the two lists)
+            for (size_t q = 0; q < colsA.size(); ++q) H.pos[colsA[q]] = (int)q;
+            for (size_t q = 0; q < colsB.size(); ++q) H.pos[colsB[q]] = (int)q;
+            H.bitsA = L.bits; H.par = L.par;
+            if (stats_on()) {
                 int runs = 0, longest = 0, cur = 0;
                 for (int k = 0; k < nT; ++k) { if (L.bits[k] & 1) ++cur; else { cur = 1; } longest = std::max(longest, cur); }
                 for (int k : colsA) runs += !(L.bits[k] & 1);
@@ -1667,14 +1723,26 @@ struct DataflowChol {
                         two_phase ? " (domain)" : "");
             }
         }
-        if (env_on("DBAT_HIP_DF_TRACE") && !two_phase && hipMalloc(&d_trace, (size_t)(ntasks + 3 * nT) * 16 * sizeof(long long)) != hipSuccess) d_trace = nullptr;
-        std::vector<int> bptr(nT + 1, 0), bidx;
+        H.bptr.assign(nT + 1, 0); H.bidx.clear();
         for (int j = 0; j < nT; ++j) {
             for (int i = nT - 1; i > j; --i)
-                if (has(i, j)) bidx.push_back(i);
-            bptr[j + 1] = (int)bidx.size();
+                if (has(i, j)) H.bidx.push_back(i);
+            H.bptr[j + 1] = (int)H.bidx.size();
         }
-        if (!up(d_tasks, h_tasks) || !up(d_bk_ptr, bptr) || !up(d_bk_idx, bidx) || !up(d_rowbits, rowbits) || !up(d_toff, toff) || !up(d_bk_list, bkl))
+    }
+    // common part: nz[i] = bitset of columns k <= i with a structurally non-zero tile (i, k), i = 0..nT
+    // (row nT = right-hand side, all columns), fill included.  col_owner (empty: one rank): see build_jobs.
+    bool finish_setup(const std::vector<uint64_t> &rowbits, const std::vector<int64_t> &toff,
+                      const std::vector<int> &col_owner = std::vector<int>(), int rank = 0) {
+        Sched H;
+        schedule_host(rowbits, col_owner, rank, H);
+        if (two_phase) {
+            if (!up(d_tasksB, h_tasksB) || !up(d_rowbits_top, H.rowbits_top)) return false;
+            if (use_chain && (!up(d_chain_colsB, H.colsB) || !up(d_chain_bitsB, H.bitsB))) return false;
+        }
+        if (use_chain && (!up(d_chain_cols, H.colsA) || !up(d_chain_bits, H.bitsA) || !up(d_chain_par, H.par) || !up(d_chain_pos, H.pos))) return false;
+        if (env_on("DBAT_HIP_DF_TRACE") && !two_phase && hipMalloc(&d_trace, (size_t)(ntasks + 3 * nT) * 16 * sizeof(long long)) != hipSuccess) d_trace = nullptr;
+        if (!up(d_tasks, h_tasks) || !up(d_bk_ptr, H.bptr) || !up(d_bk_idx, H.bidx) || !up(d_rowbits, rowbits) || !up(d_toff, toff) || !up(d_bk_list, H.bkl))
             return false;
         if (hipMalloc(&d_flags, ((size_t)(nT + 1) * nT + (size_t)nparts + 4 * (size_t)nT) * sizeof(int)) != hipSuccess) return false;   // tiles, helper slots, T of the sum-only tasks, T' of the diagonal tiles, claims
         if (nparts > 0 && hipMalloc(&d_parts, (size_t)nparts * 4096 * sizeof(double)) != hipSuccess) return false;
@@ -1704,8 +1772,74 @@ struct DataflowChol {
     // adj: symmetric co-visibility bitsets of the nc cameras (adj_words 64-bit words per camera);
     // nd: the nested-dissection order of the cameras (nd.hpp; with nd.nparts > 1 its blocks carry the rank
     // that owns them); unknowns: 6 per camera, then nio dense IO unknowns.
+    // Two halves.  symbolic_permuted: the row of every camera (blocks, joins), the tile pattern with its fill, the compact
+    // layout -- host only, nothing of the device is touched, so an order can be laid out and scored (nd_select, nd.hpp)
+    // before one is chosen.  setup_permuted: that, the schedule, and the uploads.
+    struct Symbolic {
+        std::vector<int> iperm, col_owner;
+        std::vector<uint64_t> rb;
+        std::vector<int64_t> toff;
+        std::vector<DfTask> tile_ij;
+    };
+    // Counts of a tile pattern: the longest dependent chain of tile columns (depth of the elimination tree: the parent of
+    // a column is its first tile row below the diagonal), the longest run of columns whose parent is the next column (what
+    // one workgroup of the chain role walks), the tile products without the right-hand-side row.
+    struct PatternStats { int etree_depth = 0, longest_run = 0; long long products = 0; };
+    PatternStats pattern_stats(const std::vector<uint64_t> &rb) const {
+        PatternStats st;
+        std::vector<int> depth(nT, 1);
+        int cur = 0;
+        for (int k = 0; k < nT; ++k) {
+            int par = -1;
+            for (int i = k + 1; i < nT; ++i) {
+                if (!((rb[(size_t)i * W + (k >> 6)] >> (k & 63)) & 1ull)) continue;
+                if (par < 0) par = i;
+                for (int w = 0; w <= (k >> 6); ++w) {
+                    uint64_t m = rb[(size_t)i * W + w] & rb[(size_t)k * W + w];
+                    if (w == (k >> 6)) m &= (1ull << (k & 63)) - 1;
+                    st.products += __builtin_popcountll(m);
+                }
+            }
+            for (int w = 0; w <= (k >> 6); ++w) {       // the diagonal tile's own sum
+                uint64_t m = rb[(size_t)k * W + w];
+                if (w == (k >> 6)) m &= (1ull << (k & 63)) - 1;
+                st.products += __builtin_popcountll(m);
+            }
+            st.etree_depth = std::max(st.etree_depth, depth[k]);
+            if (par >= 0) depth[par] = std::max(depth[par], depth[k] + 1);
+            cur = cur > 0 ? cur : 1;
+            st.longest_run = std::max(st.longest_run, cur);
+            cur = par == k + 1 ? cur + 1 : 0;
+        }
+        return st;
+    }
     bool setup_permuted(int nc, int nio, const uint64_t *adj, int adj_words, const NdTree &nd, int rank) {
         release();
+        Symbolic Y;
+        symbolic_permuted(nc, nio, adj, adj_words, nd, Y);
+        const std::vector<int> &block_end = nd.block_end;
+        if (!up(d_tile_ij, Y.tile_ij) || !up(d_iperm, Y.iperm)) return false;
+        if (hipMalloc(&d_tiles, (size_t)ntiles * 4096 * sizeof(double)) != hipSuccess) return false;
+        (void)hipMemset(d_tiles, 0, (size_t)ntiles * 4096 * sizeof(double));     // right-hand-side tiles: only their first row is ever written
+        if (hipMalloc(&d_qperm, (size_t)nT * CHOL_NB * sizeof(double)) != hipSuccess) return false;
+        if (env_on("DBAT_HIP_PLAN_STATS"))
+            fprintf(stderr, "[chol] order %d (%d with block padding, %zu blocks), %d tile rows, %d tiles (%.1f MB), dense lower triangle would be %d tiles\n",
+                    n_nat, n, block_end.size(), nT, ntiles, ntiles * 32768.0 / 1e6, nT * (nT + 1) / 2 + nT);
+        if (env_on("DBAT_HIP_PLAN_STATS")) {
+            fprintf(stderr, "[chol] cameras per block, last (root separator) first:");
+            for (size_t b = block_end.size(); b-- > 0 && block_end.size() - b <= 24;)
+                fprintf(stderr, " %d", block_end[b] - (b ? block_end[b - 1] : 0));
+            fprintf(stderr, "\n");
+        }
+        if (env_on("DBAT_HIP_PLAN_STATS") && !Y.col_owner.empty()) {
+            int ntop = 0, nmine = 0;
+            for (int k = 0; k < nT; ++k) { ntop += Y.col_owner[k] < 0; nmine += Y.col_owner[k] == rank; }
+            fprintf(stderr, "[chol] rank %d of %d: %d tile columns in its domain, %d top columns, %lld top tiles (%.1f MB summed over the ranks per factorisation)\n",
+                    rank, nd.nparts, nmine, ntop, (long long)n_top_tiles, n_top_tiles * 32768.0 / 1e6);
+        }
+        return finish_setup(Y.rb, Y.toff, Y.col_owner, rank);
+    }
+    void symbolic_permuted(int nc, int nio, const uint64_t *adj, int adj_words, const NdTree &nd, Symbolic &Y) {
         permuted = true;
         n_nat = 6 * nc + nio;
         const std::vector<int> &order = nd.order, &block_end = nd.block_end;
@@ -1739,14 +1873,16 @@ struct DataflowChol {
         n = (io0 + nio + CHOL_NB - 1) / CHOL_NB * CHOL_NB;
         nT = n / CHOL_NB; W = (nT + 64) / 64;
         perm.assign(n_nat, 0);
-        std::vector<int> iperm((size_t)n, -1);
+        std::vector<int> &iperm = Y.iperm;
+        iperm.assign((size_t)n, -1);
         for (int c = 0; c < nc; ++c)
             for (int a = 0; a < 6; ++a) perm[6 * c + a] = rowpos[c] + a;
         for (int u = 0; u < nio; ++u) perm[6 * nc + u] = io0 + u;
         for (int z = 0; z < n_nat; ++z) iperm[perm[z]] = z;
         auto pos6 = [&](int c) { return rowpos[c]; };
         // ---- tile pattern of P S P' (lower), IO rows and the right-hand side dense, then symbolic fill
-        std::vector<uint64_t> rb((size_t)(nT + 1) * W, 0);
+        std::vector<uint64_t> &rb = Y.rb;
+        rb.assign((size_t)(nT + 1) * W, 0);
         auto setbit = [&](int i, int k) { rb[(size_t)i * W + (k >> 6)] |= 1ull << (k & 63); };
         for (int a = 0; a < nc; ++a) {
             const int ta0 = pos6(a) / CHOL_NB, ta1 = (pos6(a) + 5) / CHOL_NB;
@@ -1778,7 +1914,8 @@ struct DataflowChol {
         }
         // ---- several ranks: the rank that owns every tile column (a block starts on a tile boundary, so a tile
         // column lies in one block); -1: top separator, IO unknowns
-        std::vector<int> col_owner;
+        std::vector<int> &col_owner = Y.col_owner;
+        col_owner.clear();
         if (nd.nparts > 1) {
             col_owner.assign(nT, -1);
             size_t b = 0;
@@ -1790,8 +1927,9 @@ struct DataflowChol {
         }
         // ---- compact tile storage, column-major over the pattern; the tiles of the top columns last and
         // contiguous (what the ranks sum between the two launches)
-        std::vector<int64_t> toff((size_t)(nT + 1) * nT, -1);
-        std::vector<DfTask> tile_ij;
+        std::vector<int64_t> &toff = Y.toff;
+        std::vector<DfTask> &tile_ij = Y.tile_ij;
+        toff.assign((size_t)(nT + 1) * nT, -1); tile_ij.clear();
         for (int pass = 0; pass < 2; ++pass) {
             if (pass == 1) top_tile0 = (int64_t)tile_ij.size();
             for (int k = 0; k < nT; ++k) {
@@ -1805,26 +1943,6 @@ struct DataflowChol {
         }
         ntiles = (int)tile_ij.size();
         n_top_tiles = ntiles - top_tile0;
-        if (!up(d_tile_ij, tile_ij) || !up(d_iperm, iperm)) return false;
-        if (hipMalloc(&d_tiles, (size_t)ntiles * 4096 * sizeof(double)) != hipSuccess) return false;
-        (void)hipMemset(d_tiles, 0, (size_t)ntiles * 4096 * sizeof(double));     // right-hand-side tiles: only their first row is ever written
-        if (hipMalloc(&d_qperm, (size_t)nT * CHOL_NB * sizeof(double)) != hipSuccess) return false;
-        if (env_on("DBAT_HIP_PLAN_STATS"))
-            fprintf(stderr, "[chol] order %d (%d with block padding, %zu blocks), %d tile rows, %d tiles (%.1f MB), dense lower triangle would be %d tiles\n",
-                    n_nat, n, block_end.size(), nT, ntiles, ntiles * 32768.0 / 1e6, nT * (nT + 1) / 2 + nT);
-        if (env_on("DBAT_HIP_PLAN_STATS")) {
-            fprintf(stderr, "[chol] cameras per block, last (root separator) first:");
-            for (size_t b = block_end.size(); b-- > 0 && block_end.size() - b <= 24;)
-                fprintf(stderr, " %d", block_end[b] - (b ? block_end[b - 1] : 0));
-            fprintf(stderr, "\n");
-        }
-        if (env_on("DBAT_HIP_PLAN_STATS") && !col_owner.empty()) {
-            int ntop = 0, nmine = 0;
-            for (int k = 0; k < nT; ++k) { ntop += col_owner[k] < 0; nmine += col_owner[k] == rank; }
-            fprintf(stderr, "[chol] rank %d of %d: %d tile columns in its domain, %d top columns, %lld top tiles (%.1f MB summed over the ranks per factorisation)\n",
-                    rank, nd.nparts, nmine, ntop, (long long)n_top_tiles, n_top_tiles * 32768.0 / 1e6);
-        }
-        return finish_setup(rb, toff, col_owner, rank);
     }
     // Z = inv(P S P') on the pattern of the factor, after solve() in the compact (permuted) layout on the same stream.
     // Overwrites the factor's off-diagonal tiles with M = L L_kk^-1.  One rank only.  false: out of device memory.
@@ -1956,5 +2074,28 @@ struct DataflowChol {
                                qscale, dz_out, d_parts, nparts, d_bk_list, nbk, 2, DfChain{});
     }
 };
+
+// The scorer of nd_select (nd.hpp): an order laid out in tiles and scheduled on the host, nothing on the device.  The
+// modelled time is the simulated list schedule of the whole pattern as one task list (with several ranks too: the
+// score must not depend on the rank); beyond a million tile products, where eight simulated orders per candidate
+// would show in the plan time, the estimate that decides the chain role.
+inline void df_score_order(int nc, int nio, const uint64_t *adj, int adj_words, const NdTree &T, NdScore &sc) {
+    DataflowChol D;
+    D.quiet = true;
+    DataflowChol::Symbolic Y;
+    D.symbolic_permuted(nc, nio, adj, adj_words, T, Y);
+    const DataflowChol::PatternStats st = D.pattern_stats(Y.rb);
+    sc.cams = nc; sc.blocks = (int)T.block_end.size(); sc.tile_cols = D.nT; sc.tiles = D.ntiles;
+    sc.chain = st.etree_depth; sc.run = st.longest_run; sc.products = st.products;
+    if (st.products > 1000000) {
+        sc.model = 1;
+        sc.model_us = std::max(st.etree_depth * 17.0, (double)st.products * 2.6 / std::min(D.grid, 256));
+    } else {
+        DataflowChol::Sched H;
+        D.schedule_host(Y.rb, std::vector<int>(), 0, H);
+        sc.model = 0;
+        sc.model_us = D.sim_schedule_us.empty() ? 0.0 : D.sim_schedule_us[0];
+    }
+}
 
 }  // namespace dbat

@@ -38,6 +38,9 @@ namespace dbat {
 
 static thread_local std::string g_err;
 
+// the host plan (plan.hpp: no device code) scores the candidate orders of the dissection with the model of chol_df.hpp
+static const bool g_nd_score_registered = (nd_score_hook() = df_score_order, true);
+
 struct DeviceError { std::string msg; };
 struct UsageError { std::string msg; };
 

@@ -170,6 +170,36 @@ int dbat_hip_debug_batch_stats(const dbat_hip_problem *prob, int64_t *out) {
     API_CATCH
 }
 
+/* Host only (debug / CPU unit tests): the nested dissection with the separators of `mode` (nd.hpp: 0, 1, 2) and with the
+ * ones the model chooses (whatever DBAT_HIP_ND_SEP says), each laid out in tiles and scored on the host.  out[24], twelve
+ * numbers for the requested mode and twelve for the choice: { cameras, blocks, tile columns, tiles, longest chain (depth
+ * of the elimination tree in tile columns), tile products (without the right-hand-side row), modelled time (us), the mode,
+ * nd_check (0: a permutation whose co-visible cameras always lie on one root path of the block tree), longest run of
+ * consecutive columns, model (0: list schedule, 1: chain / products estimate), 0 }. */
+int dbat_hip_debug_nd_stats(const dbat_hip_problem *prob, int32_t mode, double *out) {
+    API_TRY
+    if (!prob || !out || mode < 0 || mode > 2) { g_err = "null argument or mode not 0, 1, 2"; return DBAT_HIP_EINVAL; }
+    Plan P;
+    if (!build_plan(*prob, P, false)) { g_err = P.err; return DBAT_HIP_EINVAL; }
+    const bool nd_off = env_on("DBAT_HIP_ND_OFF");
+    const int nparts = P.mg_subtree ? P.nranks : 1;
+    auto put = [&](const NdTree &T, NdScore sc, int m, double *o) {
+        if (sc.mode != m) df_score_order(P.nc, P.nIOu, P.cam_adj.data(), P.cam_adj_words, T, sc);
+        const double v[12] = {(double)sc.cams, (double)sc.blocks, (double)sc.tile_cols, (double)sc.tiles, (double)sc.chain, (double)sc.products,
+                              sc.model_us, (double)m, (double)nd_check(P.nc, P.cam_adj.data(), P.cam_adj_words, T), (double)sc.run, (double)sc.model, 0.0};
+        std::copy(v, v + 12, o);
+    };
+    NdTree T;
+    nd_build(P.nc, P.cam_adj.data(), P.cam_adj_words, P.nd_xyz.data(), P.nd_weight.data(), nparts, P.nd_leaf, nd_off, mode, T);
+    put(T, NdScore(), mode, out);
+    NdScore sc[3];
+    const int chosen = nd_select(P.nc, P.nIOu, P.cam_adj.data(), P.cam_adj_words, P.nd_xyz.data(), P.nd_weight.data(), nparts, P.nd_leaf, nd_off,
+                                 -1, true, T, sc);
+    put(T, sc[chosen], chosen, out + 12);
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
 /* Host evaluation of the per-observation model (debug / CPU unit tests of
  * model.hpp only; never used by the product path). */
 int dbat_hip_debug_model_eval_host(int32_t model, int32_t nK, int32_t nP, const double *EO6, const double *IO,

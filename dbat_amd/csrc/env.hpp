@@ -35,11 +35,13 @@ static const EnvSwitch kEnvSwitches[] = {
     {"DBAT_HIP_MG_REPLICATED", false, "several ranks: envelope summed, replicated factorisation"},
     {"DBAT_HIP_ND_OFF", false, "no nested dissection"},
     {"DBAT_HIP_ND_LEAF", false, "leaf size of the dissection"},
+    {"DBAT_HIP_ND_SEP", false, "separators inside a domain: 0 = lower boundary at the median, 1 = minimum vertex cover at the median, 2 = minimum cover with slid cuts (default: the one the model of the factorisation prefers)", "0|1|2"},
     {"DBAT_HIP_ND_PAD_ALL", false, "every block of the dissection on a tile boundary"},
     {"DBAT_HIP_ND_JOIN_SMALL", false, "separators up to that many rows join their child's last tile"},
     {"DBAT_HIP_DF_SPLIT", false, "factorisation: helper tasks for sums longer than this many products (default 96)"},
     {"DBAT_HIP_DF_CHUNK", false, "factorisation: products per helper task (default 32)"},
     {"DBAT_HIP_DF_CHAIN", false, "factorisation: 0 = diagonal tiles as ordinary tasks (no chain role), 1 = chain role whatever the pattern", "0|1"},
+    {"DBAT_HIP_DF_MERGE", false, "factorisation: sums of the columns where two parts of the dissection meet cut into early and late pieces: 0 = never, 1 = wherever the chain role is on (default: where the simulated schedule is shorter)", "0|1"},
     {"DBAT_HIP_DF_CHAIN_WG", false, "factorisation: workgroups of the chain role at most (default 32)"},
     {"DBAT_HIP_DF_L2", false, "factorisation: 1 = finished tiles of the compact layout are read through the L2", "0|1"},
     {"DBAT_HIP_COV_DENSE", false, "posterior covariance: the dense inverse of the reduced system (rocsolver_dpotri) instead of the selected inversion"},

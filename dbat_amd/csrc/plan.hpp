@@ -136,6 +136,10 @@ struct Plan {
     // with several ranks, the domain of every rank (mg_subtree: object points follow their cameras' domain,
     // the domains factor locally and only the top separators' Schur complement is summed over the ranks)
     NdTree nd;
+    int nd_sep = 0;                                // the separators it was built with (nd.hpp: 0, 1, 2) ...
+    NdScore nd_score[3];                           // ... and the candidates the model scored to choose them (mode < 0: not scored)
+    std::vector<double> nd_xyz, nd_weight;         // what the dissection was steered by (dbat_hip_debug_nd_stats builds the other modes)
+    int nd_leaf = 32;
     bool mg_subtree = false;
     int max_k = 0;                                 // max observations of one point
     bool shared_eo = false;                        // EO.struct.block shares elements between images (camera stations):
@@ -972,7 +976,19 @@ inline bool build_plan(const dbat_hip_problem &pb, Plan &P, bool with_obs) {
             wcam[c] = (double)n_cam[c];
         }
         const int leaf = std::max(8, env_int("DBAT_HIP_ND_LEAF", 32));
-        nd_build(nc, P.cam_adj.data(), P.cam_adj_words, xyz.data(), wcam.data(), P.mg_subtree ? P.nranks : 1, leaf, nd_off, P.nd);
+        // the separators inside a domain (nd.hpp): DBAT_HIP_ND_SEP, or the candidate the model of the factorisation prefers
+        // (shared EO blocks factor in place: the order only cuts the domains)
+        const bool stats = env_on("DBAT_HIP_PLAN_STATS");
+        const int forced = permuted_ok ? env_int("DBAT_HIP_ND_SEP", -1) : 0;
+        P.nd_sep = nd_select(nc, P.nIOu, P.cam_adj.data(), P.cam_adj_words, xyz.data(), wcam.data(), P.mg_subtree ? P.nranks : 1, leaf, nd_off,
+                             forced, stats, P.nd, P.nd_score);
+        for (int m = 0; m < 3 && stats; ++m)
+            if (P.nd_score[m].mode == m)
+                fprintf(stderr, "[plan] separators %d (%s): %d tile columns, %d tiles, longest chain %d, %lld tile products, modelled %.0f us (%s)%s\n",
+                        m, m == 0 ? "lower boundary at the median" : m == 1 ? "minimum cover at the median" : "minimum cover, slid cuts",
+                        P.nd_score[m].tile_cols, P.nd_score[m].tiles, P.nd_score[m].chain, P.nd_score[m].products, P.nd_score[m].model_us,
+                        P.nd_score[m].model ? "chain / products estimate" : "list schedule", m == P.nd_sep ? (forced >= 0 && forced <= 2 ? "  <- DBAT_HIP_ND_SEP" : "  <- chosen") : "");
+        P.nd_xyz.swap(xyz); P.nd_weight.swap(wcam); P.nd_leaf = leaf;
     }
     lapt("nested dissection");
     // Points that fit a tile of the MFMA Schur kernel (at most CMAX cameras and
