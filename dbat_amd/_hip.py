@@ -203,6 +203,8 @@ SYMBOLS = {
     'dbat_hip_residual_stats': (C.c_int, [_H, _dp, _lp, _dp, _lp, _dp, _dp, _dp, _lp]),
     'dbat_hip_quality_hull_cap': (C.c_int32, []),
     'dbat_hip_debug_coverage_host': (C.c_int, [C.POINTER(Problem), _dp, _dp, _dp, _lp, _dp, _lp, _lp]),
+    'dbat_hip_debug_df_schedule': (C.c_int, [C.POINTER(Problem), _lp, _dp, _ip, C.c_int64, _ip, C.c_int64,
+                                             C.POINTER(C.c_uint64), C.c_int64]),
     'dbat_hip_default_robust_options': (C.c_int, [C.c_int32, C.POINTER(RobustOptions)]),
     'dbat_hip_robust_weights': (C.c_int, [_H, _dp, C.POINTER(RobustOptions), _dp, _dp, _dp]),
     'dbat_hip_set_obs_weights': (C.c_int, [_H, _dp]),
@@ -1145,6 +1147,31 @@ def nd_stats(s, mode, shard_rank=0, shard_count=1):
                           products=int(v[5]), model_us=float(v[6]), mode=int(v[7]), valid=int(v[8]) == 0, run=int(v[9]),
                           model='estimate' if v[10] else 'list schedule')
     return part(out[:12]), part(out[12:])
+
+
+def df_schedule(s):
+    """Host-only (debug): the task list of the factorisation in the compact tile layout on one rank, as a handle would
+    schedule it for this struct (dbat_hip_debug_df_schedule; DBAT_HIP_DF_SUMS and DBAT_HIP_DF_MERGE honoured).  Returns a
+    dict: nT, W, jobs (int array [tasks, 8]: i, k, jlo, jhi, part, np, mode, p in task order), plist (the product lists),
+    listed_bit (the bit of mode that marks a task whose products are plist[jlo:jhi]), rowbits (uint64 [(nT + 1), W]: bit
+    k of row i = tile (i, k) exists), cand_us (modelled microseconds of: column order, sums cut at the merge columns,
+    product lists, lists and cut sums; < 0: not made), taken (index into cand_us), nparts, products, chain_role,
+    chain_tiles, n_listed."""
+    lib = load()
+    p, keep = problem_from_struct(s)
+    hdr = np.zeros(16, np.int64)
+    cand = np.zeros(4)
+    null_i, null_u = C.cast(None, _ip), C.cast(None, C.POINTER(C.c_uint64))
+    check(lib.dbat_hip_debug_df_schedule(C.byref(p), hdr.ctypes.data_as(_lp), dptr(cand), null_i, 0, null_i, 0, null_u, 0))
+    nT, W, nt, nl = (int(v) for v in hdr[:4])
+    jobs = np.zeros((max(nt, 1), 8), np.int32)
+    plist = np.zeros(max(nl, 1), np.int32)
+    rb = np.zeros(((nT + 1), W), np.uint64)
+    check(lib.dbat_hip_debug_df_schedule(C.byref(p), hdr.ctypes.data_as(_lp), dptr(cand), jobs.ctypes.data_as(_ip), jobs.size,
+                                         plist.ctypes.data_as(_ip), plist.size, rb.ctypes.data_as(C.POINTER(C.c_uint64)), rb.size))
+    return dict(nT=nT, W=W, jobs=jobs[:nt], plist=plist[:nl], listed_bit=int(hdr[10]), rowbits=rb, cand_us=[float(v) for v in cand],
+                taken=int(hdr[4]), nparts=int(hdr[5]), products=int(hdr[6]), chain_role=bool(hdr[7]), chain_tiles=int(hdr[8]),
+                n_listed=int(hdr[9]))
 
 
 def batch_stats(s, shard_rank=0, shard_count=1):

@@ -69,6 +69,10 @@ struct DfTask { int i, k; };
 // T_r = A_r(i,k) - sum over the columns j of the rank's OWN domain, is left in the tile and summed over the
 // ranks before the top separators are factored (phase B, every rank).  | 8: no identity on the padding rows
 // (they are contributed by rank 0 only).
+// | DF_LISTED (one rank, compact tiles, chain role on): the products are not the common columns of [jlo, jhi) in column
+// order but the entries [jlo, jhi) of the plan's product list (DfChain::plist), in the order the schedule's model expects
+// their tiles to exist (order_jobs).  The order is fixed at plan time: the summation order of a tile never depends on the run.
+constexpr int DF_LISTED = 32;
 struct DfJob { int i, k, jlo, jhi, part, np, mode, p; };
 
 // Tiles that one workgroup writes and others read inside the same launch move
@@ -572,6 +576,7 @@ struct DfChain {
     const int *pos;      // [nT] position of column k in cols
     int ncols, nwg, ctr_slot, role_slot;
     int trace_potf2;     // measurement build: clocks inside df_potf2 as well (they cost about a microsecond per factorisation)
+    const int *plist;    // product columns of the DF_LISTED jobs (DfJob): only a launch with the chain role has such jobs
 };
 
 // T'(k,k) in the accumulator layout of mfma_tile64: element (c = 16 ty + (tx >> 4) + 4 e, r = 16 rt + (tx & 15)).
@@ -835,6 +840,10 @@ __global__ __launch_bounds__(256) void k_chol_df(DfView V, int n, int nT, const 
         const DfJob jb = tasks[task];
         const int i = jb.i, k = jb.k;
         const bool helper = jb.np < 0;                  // a piece of a long sum (see DfJob)
+        // (listed jobs exist only where the chain role is on: the all-task instantiation, which the tile products bind,
+        // keeps the code it had -- its time moves by several per cent with any change to this loop)
+        const bool listed = CHAIN && (jb.mode & DF_LISTED) != 0;    // its products: entries [jlo, jhi) of C.plist
+        const int mode = CHAIN ? jb.mode & ~DF_LISTED : jb.mode;
         const int jend = jb.jhi;                        // products j in [jb.jlo, jend) (owner of a whole sum: jhi = k)
         int *pflags = flags + (int64_t)(nT + 1) * nT;   // flags of the helpers' partial sums
         int *tflags = pflags + nparts;                  // per column: T of its sum-only task (DfJob mode 1) is in the tile
@@ -875,9 +884,14 @@ __global__ __launch_bounds__(256) void k_chol_df(DfView V, int n, int nT, const 
             if (w == (jend >> 6)) m &= (1ull << (jend & 63)) - 1;
             return m;
         };
-        int jw = jb.jlo >> 6;
-        uint64_t jm = jend > jb.jlo ? word(jw) : 0ull;
+        int jw = listed ? 0 : jb.jlo >> 6;
+        uint64_t jm = !listed && jend > jb.jlo ? word(jw) : 0ull;
+        int lp = jb.jlo;                                // listed: the next entry of the product list
+        // A listed job walks its products in the plan's order instead of column order.  The deadlock argument is
+        // unchanged: a task still waits only for tiles of tasks with smaller numbers or of chain columns taken by
+        // ticket -- the order in which it waits for its own inputs does not change which inputs they are.
         auto next_j = [&]() -> int {                    // next common column in [jlo, jend), -1 at the end
+            if (listed) return lp < jend ? C.plist[lp++] : -1;
             for (;;) {
                 if (jm) { const int j = 64 * jw + __builtin_ctzll(jm); jm &= jm - 1; return j; }
                 if (jend <= jb.jlo || ++jw > wend) return -1;
@@ -1034,7 +1048,7 @@ __global__ __launch_bounds__(256) void k_chol_df(DfView V, int n, int nT, const 
             __syncthreads();
             continue;
         }
-        if (jb.mode == 1 || jb.mode == 16) {            // sum only: T -> the tile; the diagonal task of the column finishes it
+        if (mode == 1 || mode == 16) {            // sum only: T -> the tile; the diagonal task of the column finishes it
                                                         // (16: T' of the diagonal tile itself, for the chain role)
 #pragma unroll
             for (int rt = 0; rt < 4; ++rt)
@@ -1046,7 +1060,7 @@ __global__ __launch_bounds__(256) void k_chol_df(DfView V, int n, int nT, const 
             if (trace && t == 0) trace[task * 16 + 3] = wall_clock64();
             __builtin_amdgcn_s_waitcnt(0);
             __syncthreads();
-            if (t == 0) __hip_atomic_store(jb.mode == 1 ? tflags + k : C.dflags + k, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (t == 0) __hip_atomic_store(mode == 1 ? tflags + k : C.dflags + k, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (trace && t == 0) trace[task * 16 + 4] = wall_clock64();
             continue;
         }
@@ -1069,7 +1083,7 @@ __global__ __launch_bounds__(256) void k_chol_df(DfView V, int n, int nT, const 
                 const int zn = V.iperm ? V.iperm[col0 + tx] : (int)(col0 + tx);
                 if (zn >= 0) ldiag[zn] = smem[tx * DF_TLD + tx];
             }
-            if (jb.mode == 2) {
+            if (mode == 2) {
                 __syncthreads();                        // the pivots have been read: the L rows may go
                 // The next link of the chain, here instead of in a second workgroup: L(p,k) = T(p,k) L^-T with
                 // T from the column's sum-only task (published long ago as a rule) and L^-T where df_potf2
@@ -1291,6 +1305,10 @@ struct DataflowChol {
     int64_t top_tile0 = 0, n_top_tiles = 0;             // the tiles of the top columns are the last n_top_tiles of d_tiles
     std::vector<double> sim_critical_us, sim_schedule_us;   // per task list: critical path / simulated list schedule (model, us)
     std::vector<DfJob> h_tasksB;
+    std::vector<int> h_plist;                           // product columns of the listed jobs (DfJob, DF_LISTED)
+    int *d_plist = nullptr;
+    double cand_us[4] = {-1.0, -1.0, -1.0, -1.0};       // one rank: modelled time of column order / sums cut / product lists / lists and cut sums (< 0: not made)
+    int cand_taken = 0;                                 // ... and the one the schedule is
     DfTask *d_tile_ij = nullptr;
     int nparts = 0;                                     // partial-sum slots of the helper tasks
     bool env_l2 = false;                                // finished tiles through the L2: measured in round 2, no gain (kept off)
@@ -1318,11 +1336,11 @@ struct DataflowChol {
     void release() {
         void *ps[] = {d_flags, d_ctl, d_bk_ptr, d_bk_idx, d_iperm, d_toff, d_rowbits, d_tasks, d_tile_ij, d_tiles, d_qperm, d_parts,
                       d_tasksB, d_bk_list, d_rowbits_top, d_chain_cols, d_chain_colsB, d_chain_par, d_chain_bits, d_chain_bitsB, d_chain_pos,
-                      d_ztiles, d_si_m, d_si_off, d_si_diag, d_perm};
+                      d_ztiles, d_si_m, d_si_off, d_si_diag, d_perm, d_plist};
         for (void *p : ps) if (p) (void)hipFree(p);
         d_flags = d_ctl = d_bk_ptr = d_bk_idx = d_iperm = nullptr; d_toff = nullptr; d_rowbits = nullptr;
         d_tasks = nullptr; d_tile_ij = nullptr; d_tiles = d_qperm = d_parts = nullptr;
-        d_tasksB = nullptr; d_bk_list = nullptr; d_rowbits_top = nullptr;
+        d_tasksB = nullptr; d_bk_list = nullptr; d_rowbits_top = nullptr; d_plist = nullptr;
         d_chain_cols = d_chain_colsB = d_chain_par = d_chain_bits = d_chain_bitsB = d_chain_pos = nullptr;
         d_ztiles = nullptr; d_si_m = d_si_off = nullptr; d_si_diag = d_perm = nullptr; n_si_m = 0;
         si_off_ptr.clear(); si_diag_ptr.clear();
@@ -1366,7 +1384,17 @@ struct DataflowChol {
     // One task list (see DfJob).  PHASE 0: the whole factorisation (one rank).  Several ranks (col_owner: the
     // rank whose domain a tile column belongs to, -1 = top separator / IO): PHASE 1 = the columns of this rank's
     // domain and its share of every top tile (mode 4); PHASE 2 = the top columns, products over top columns only.
-    struct JobList { std::vector<DfJob> jobs; std::vector<int> dptr, dep, own, sumjob, presum, bits, par; };
+    // pj: the column of every product (two entries of dep each).  What order_jobs leaves: the jobs in task order, ord
+    // (the number build_jobs gave the job at each place), the modelled time with every sum in column order (t_col) and
+    // with the product lists (t_list; < 0: none made) in the task order ord_list, walk (per product slot: the place in
+    // column order of the product taken then) and listed (per job as numbered by build_jobs: its walk is a list of its
+    // own) -- apply_lists.
+    struct JobList {
+        std::vector<DfJob> jobs; std::vector<int> dptr, dep, own, sumjob, presum, bits, par;
+        std::vector<int> pj, ord, ord_list, walk; std::vector<char> listed;
+        double t_col = 0.0, t_list = -1.0, cp = 0.0;
+        int np = 0; long long nprod = 0;                       // partial-sum slots and tile products of this list
+    };
     void build_jobs(int phase, const std::vector<uint64_t> &rowbits, const std::vector<int> &col_owner, int rank, JobList &L, int merge_depth = 0) {
         auto has = [&](int i, int k) { return (rowbits[(size_t)i * W + (k >> 6)] >> (k & 63)) & 1ull; };
         const int split_min = std::max(env_int("DBAT_HIP_DF_SPLIT", 96), 2);
@@ -1377,7 +1405,7 @@ struct DataflowChol {
         int dom_lo = nT, dom_hi = 0;                            // this rank's domain: a contiguous range of tile columns
         if (phase == 1) for (int k = 0; k < nT; ++k) if (col_owner[k] == rank) { dom_lo = std::min(dom_lo, k); dom_hi = k + 1; }
         if (dom_hi <= dom_lo) dom_lo = dom_hi = 0;
-        L.jobs.clear(); L.dptr.assign(1, 0); L.dep.clear();
+        L.jobs.clear(); L.dptr.assign(1, 0); L.dep.clear(); L.pj.clear();
         L.own.assign((size_t)(nT + 1) * nT, -1); L.sumjob.assign(nT, -1);
         L.presum.assign(nT, -1); L.bits.assign(nT, 0); L.par.assign(nT, -1);
         const bool chain = use_chain && merge;
@@ -1404,7 +1432,7 @@ struct DataflowChol {
             // emit the job(s) of tile (i,k) with the products js; returns the owner job
             auto emit = [&](int i, int mode, int par, int jhi_owner) {
                 auto push_products = [&](int q0, int q1) {
-                    for (int q = q0; q < q1; ++q) { L.dep.push_back(L.own[(size_t)k * nT + js[q]]); L.dep.push_back(i != k ? L.own[(size_t)i * nT + js[q]] : -1); }
+                    for (int q = q0; q < q1; ++q) { L.dep.push_back(L.own[(size_t)k * nT + js[q]]); L.dep.push_back(i != k ? L.own[(size_t)i * nT + js[q]] : -1); L.pj.push_back(js[q]); }
                     L.dptr.push_back((int)L.dep.size());
                 };
                 n_products += (long long)js.size();
@@ -1485,7 +1513,12 @@ struct DataflowChol {
     // workgroups then sit in the dependent chains of a few leaves while the other leaves
     // have not started.  Candidate orders are tried on a model of the kernel (measured
     // costs, us: bench/chol_trace.py, bench/chol_path.py) and the best one is taken.
-    void order_jobs(JobList &L, const char *what) {
+    // sums (DBAT_HIP_DF_SUMS; 0 wherever the layout is not the compact one on one rank): 0 no product lists; 1 / -1 the
+    // lists of the model -- the best task order is simulated in column order, every job's products are sorted by the
+    // time both tiles exist in that simulation (ties by column), and the schedule is simulated again with the lists
+    // FIXED, exactly as the device walks them; up to three rounds while the time falls, the best round is kept;
+    // 2 / 3: every job a list in ascending / descending column order (control / tests).
+    void order_jobs(JobList &L, const char *what, int sums = 0) {
         std::vector<DfJob> &jobs = L.jobs;
         const std::vector<int> &dptr = L.dptr, &dep = L.dep, &own = L.own, &sumjob = L.sumjob;
         const int nt = (int)jobs.size();
@@ -1526,14 +1559,17 @@ struct DataflowChol {
         // The kernel as a list schedule: `workers` resident workgroups take the tasks in order; a
         // workgroup consumes its inputs in its fixed order, every product after both tiles exist.
         const int workers = std::max(1, std::min(grid, 256));      // 400 registers per lane: one workgroup per CU
+        std::vector<double> done;
+        const std::vector<int> *walk = nullptr;                 // the products of a job in this order (nullptr: column order)
         auto simulate = [&](const std::vector<int> &ord) {
-            std::vector<double> done(nt, 0.0);
+            done.assign(nt, 0.0);
             std::priority_queue<double, std::vector<double>, std::greater<double>> freeat;
             for (int w = 0; w < workers; ++w) freeat.push(0.0);
             double last = 0.0;
             for (int t : ord) {
                 double tc = freeat.top(); freeat.pop();
-                for (int q = dptr[t]; q + 1 < dptr[t + 1]; q += 2) {
+                for (int a = dptr[t] / 2; a < dptr[t + 1] / 2; ++a) {
+                    const int q = walk ? dptr[t] + 2 * (*walk)[a] : 2 * a;
                     double av = done[dep[q]];
                     if (dep[q + 1] >= 0) av = std::max(av, done[dep[q + 1]]);
                     tc = std::max(tc, av + c_hop) + c_prod;
@@ -1581,7 +1617,7 @@ struct DataflowChol {
         };
         const double betas[] = {0.0, 0.25, 0.5, 1.0, 2.0, 4.0, 1e6};
         const int ncand = (int)(sizeof(betas) / sizeof(betas[0])) + 1;
-        std::vector<int> best_ord;
+        std::vector<int> best_ord, list_ords[2];               // (list_ords: the orders of the keys 0 and 3, for the product lists)
         double tbest = 1e300;
         int best = -1;
         std::vector<double> key(nt), tcs(ncand);
@@ -1592,11 +1628,63 @@ struct DataflowChol {
             else for (int t = 0; t < nt; ++t) key[t] = est[t] - c_prod * nprod_of(t);
             std::vector<int> ord = kahn(key);
             tcs[c] = simulate(ord);
+            if (sums == 1 || sums < 0) { if (c == 0) list_ords[0] = ord; else if (c == 3) list_ords[1] = ord; }
             if (forced == c || (forced < 0 && tcs[c] < tbest)) { tbest = tcs[c]; best = c; best_ord.swap(ord); }
         }
         double cp = 0.0;
         for (int t = 0; t < nt; ++t) cp = std::max(cp, fin[t]);
         sim_critical_us.push_back(cp); sim_schedule_us.push_back(tbest);
+        L.t_col = tbest; L.t_list = -1.0; L.cp = cp;
+        L.ord_list = best_ord;
+        L.walk.clear(); L.listed.assign(nt, 0);
+        if (sums != 0) {
+            const int nslots = (int)dep.size() / 2;
+            std::vector<int> wk(nslots);
+            for (int t = 0; t < nt; ++t) for (int a = dptr[t] / 2; a < dptr[t + 1] / 2; ++a) wk[a] = a - dptr[t] / 2;
+            if (sums == 2 || sums == 3) {
+                if (sums == 3) for (int t = 0; t < nt; ++t) std::reverse(wk.begin() + dptr[t] / 2, wk.begin() + dptr[t + 1] / 2);
+                walk = &wk;
+                L.t_list = simulate(best_ord);
+                L.walk = wk;
+                for (int t = 0; t < nt; ++t) L.listed[t] = nprod_of(t) > 0;
+            } else {
+                // The lists are made for the best task order of column order and for the orders of two of the keys (the two
+                // an order that is only scored is simulated with): with lists another task order may be the shorter one.
+                std::vector<double> avail(nslots);
+                for (int lo = -1; lo < 2; ++lo) {
+                    const std::vector<int> &ord = lo < 0 ? best_ord : list_ords[lo];
+                    if (lo >= 0 && (ord.empty() || forced >= 0 || ord == best_ord)) continue;      // (a forced order stays)
+                    walk = nullptr;
+                    double tprev = simulate(ord);               // (the finish times of this order, sums in column order)
+                    for (int round = 0; round < 3; ++round) {
+                        for (int t = 0; t < nt; ++t)
+                            for (int a = dptr[t] / 2; a < dptr[t + 1] / 2; ++a) {
+                                avail[a] = done[dep[2 * a]];
+                                if (dep[2 * a + 1] >= 0) avail[a] = std::max(avail[a], done[dep[2 * a + 1]]);
+                            }
+                        for (int t = 0; t < nt; ++t) {
+                            const int a0 = dptr[t] / 2;
+                            for (int a = a0; a < dptr[t + 1] / 2; ++a) wk[a] = a - a0;
+                            std::stable_sort(wk.begin() + a0, wk.begin() + dptr[t + 1] / 2, [&](int x, int y) { return avail[a0 + x] < avail[a0 + y]; });
+                        }
+                        walk = &wk;
+                        const double tl = simulate(ord);
+                        if (L.t_list < 0.0 || tl < L.t_list) { L.t_list = tl; L.walk = wk; L.ord_list = ord; }
+                        if (!(tl < tprev)) break;
+                        tprev = tl;
+                    }
+                }
+                for (int t = 0; t < nt; ++t)                     // a list that is column order is no list
+                    for (int a = dptr[t] / 2; a < dptr[t + 1] / 2; ++a) if (L.walk[a] != a - dptr[t] / 2) L.listed[t] = 1;
+            }
+            walk = nullptr;
+            if (stats_on()) {
+                int nl = 0;
+                for (int t = 0; t < nt; ++t) nl += L.listed[t];
+                fprintf(stderr, "[chol %s] product lists (mode %d): %d of %d tasks listed, simulated %.0f us (column order %.0f us)\n", what, sums, nl, nt, L.t_list, L.t_col);
+            }
+        }
+        L.ord = best_ord;
         if (stats_on()) {
             fprintf(stderr, "[chol %s] %d tasks, critical path %.0f us; simulated with %d workgroups, key = earliest start - beta x bottom level:",
                     what, nt, cp, workers);
@@ -1608,6 +1696,24 @@ struct DataflowChol {
         for (int t = 0; t < nt; ++t) sorted[t] = jobs[best_ord[t]];
         jobs.swap(sorted);
     }
+    // The product lists of order_jobs into the jobs (now in task order): a listed job's jlo / jhi become its range of
+    // plist (DfJob, DF_LISTED), in the task order the lists were scored with; a job whose list is column order keeps its
+    // range of columns and the bit iteration.
+    static void apply_lists(JobList &L, std::vector<int> &plist) {
+        std::vector<DfJob> byno(L.jobs.size());
+        for (size_t t = 0; t < L.jobs.size(); ++t) byno[L.ord[t]] = L.jobs[t];
+        for (size_t t = 0; t < L.jobs.size(); ++t) L.jobs[t] = byno[L.ord_list[t]];      // the task order the lists were made for
+        L.ord = L.ord_list;
+        for (size_t t = 0; t < L.jobs.size(); ++t) {
+            const int o = L.ord[t];
+            if (!L.listed[o]) continue;
+            const int a0 = L.dptr[o] / 2, a1 = L.dptr[o + 1] / 2;
+            L.jobs[t].jlo = (int)plist.size();
+            for (int a = a0; a < a1; ++a) plist.push_back(L.pj[a0 + L.walk[a]]);
+            L.jobs[t].jhi = (int)plist.size();
+            L.jobs[t].mode |= DF_LISTED;
+        }
+    }
     // Host half of the schedule: task lists, chain role, tables of the backward substitution.  No device call.
     struct Sched { std::vector<int> colsA, colsB, bitsA, bitsB, par, pos, bkl, bptr, bidx; std::vector<uint64_t> rowbits_top; };
     bool quiet = false;                                 // an order that is only scored (nd_select, nd.hpp): no statistics lines, two of the candidate task orders
@@ -1617,6 +1723,8 @@ struct DataflowChol {
         if (const char *g = env_get("DBAT_HIP_DF_GRID")) grid = std::min(std::max(atoi(g), 1), 4096);
         nparts = 0; n_products = 0;
         two_phase = !col_owner.empty();
+        h_plist.clear(); cand_taken = 0;
+        for (double &c : cand_us) c = -1.0;
         h_rowbits = rowbits;
         // The chain role pays where the dependent chain of the separators decides the time (C1 ... C3: 0.61 -> 0.59 ms at C3);
         // where the tile products do (C4: 116 000 of them, 3.07 -> 3.29 ms) its workgroups and the extra sum tasks cost more
@@ -1667,24 +1775,47 @@ struct DataflowChol {
         std::vector<int> &bkl = H.bkl;                          // panels of the backward substitution, in task order
         bkl.clear(); h_tasksB.clear(); ntasksB = 0; nchain = nchainB = 0; chain_wg = chain_wgB = 0;
         if (!two_phase) {
+            // Four candidate schedules, each ordered and scored by order_jobs: 0 every sum in column order, 1 the same
+            // with the sums cut where two parts of the dissection meet (build_jobs), 2 product lists (order_jobs), 3 lists
+            // and cut sums.  An earlier candidate stays unless a later one is more than 1 % shorter in the model (cut sums:
+            // and their partial sums stay within 128 MB).  DBAT_HIP_DF_MERGE=0 / 1: never / wherever the chain role is on;
+            // DBAT_HIP_DF_SUMS=0: no lists, 1: lists, 2 / 3: every job a list in ascending / descending column order (the
+            // cut as without lists).  Lists only in the compact layout and where the chain role is on, i.e. where the waits
+            // along the dependent chain decide the time (k_chol_df<true> alone walks lists).  Where the tile products do
+            // (C4) the model, which charges every product the same, promised 4 % and the kernel lost 5 % (2.68 -> 2.81 ms).
+            const int sums = permuted && use_chain ? env_int("DBAT_HIP_DF_SUMS", -1) : 0;
             build_jobs(0, rowbits, col_owner, rank, L);
-            order_jobs(L, "all");
+            L.np = nparts; L.nprod = n_products;
+            order_jobs(L, "all", sums);
             const int force_merge = env_int("DBAT_HIP_DF_MERGE", -1);
+            JobList M;
+            bool have_cut = false;
             if (use_chain && force_merge != 0) {
-                // ... and the same with the sums cut where two parts of the dissection meet (build_jobs): kept where the
-                // simulated schedule is shorter by more than 1 % and the partial sums stay within 128 MB
-                // (DBAT_HIP_DF_MERGE=0 / 1: never / wherever the chain role is on)
-                const int np0 = nparts;
-                const long long prod0 = n_products;
-                JobList M;
                 nparts = 0; n_products = 0;
                 build_jobs(0, rowbits, col_owner, rank, M, 2);
-                order_jobs(M, "all, sums cut at the merge columns");
-                const bool better = nparts <= 4096 && (force_merge == 1 || sim_schedule_us[1] < 0.99 * sim_schedule_us[0]);
-                if (better) std::swap(L, M); else { nparts = np0; n_products = prod0; }
-                sim_critical_us.erase(sim_critical_us.begin() + (better ? 0 : 1)); sim_schedule_us.erase(sim_schedule_us.begin() + (better ? 0 : 1));
-                if (stats_on()) fprintf(stderr, "[chol] sums cut at the merge columns: %s (%d partial sums)\n", better ? "yes" : "no", nparts);
+                M.np = nparts; M.nprod = n_products;
+                order_jobs(M, "all, sums cut at the merge columns", sums);
+                have_cut = M.np <= 4096;
             }
+            cand_us[0] = L.t_col; cand_us[1] = have_cut ? M.t_col : -1.0;
+            cand_us[2] = L.t_list; cand_us[3] = have_cut ? M.t_list : -1.0;
+            const bool must_cut = have_cut && force_merge == 1;
+            int taken = must_cut || (have_cut && M.t_col < 0.99 * L.t_col) ? 1 : 0;
+            if (sums == 1) taken = must_cut || (have_cut && M.t_list < 0.99 * L.t_list) ? 3 : 2;
+            else if (sums == 2 || sums == 3) taken += 2;
+            else if (sums < 0) {
+                if (!must_cut && L.t_list >= 0.0 && L.t_list < 0.99 * cand_us[taken]) taken = 2;
+                if (have_cut && M.t_list >= 0.0 && M.t_list < 0.99 * cand_us[taken]) taken = 3;
+            }
+            cand_taken = taken;
+            if (taken & 1) std::swap(L, M);
+            nparts = L.np; n_products = L.nprod;
+            h_plist.clear();
+            if (taken >= 2) apply_lists(L, h_plist);
+            sim_critical_us.assign(1, L.cp); sim_schedule_us.assign(1, cand_us[taken]);
+            if (stats_on())
+                fprintf(stderr, "[chol] schedules: column order %.0f us, sums cut %.0f us, product lists %.0f us, lists and cut sums %.0f us -> %d (%d partial sums, %zu listed products)\n",
+                        cand_us[0], cand_us[1], cand_us[2], cand_us[3], taken, nparts, h_plist.size());
             split_chain(L, h_tasks, colsA); ntasks = (int)h_tasks.size();
             for (int j = nT - 1; j >= 0; --j) bkl.push_back(j);
         } else {
@@ -1742,6 +1873,7 @@ struct DataflowChol {
         }
         if (use_chain && (!up(d_chain_cols, H.colsA) || !up(d_chain_bits, H.bitsA) || !up(d_chain_par, H.par) || !up(d_chain_pos, H.pos))) return false;
         if (env_on("DBAT_HIP_DF_TRACE") && !two_phase && hipMalloc(&d_trace, (size_t)(ntasks + 3 * nT) * 16 * sizeof(long long)) != hipSuccess) d_trace = nullptr;
+        if (!up(d_plist, h_plist)) return false;
         if (!up(d_tasks, h_tasks) || !up(d_bk_ptr, H.bptr) || !up(d_bk_idx, H.bidx) || !up(d_rowbits, rowbits) || !up(d_toff, toff) || !up(d_bk_list, H.bkl))
             return false;
         if (hipMalloc(&d_flags, ((size_t)(nT + 1) * nT + (size_t)nparts + 4 * (size_t)nT) * sizeof(int)) != hipSuccess) return false;   // tiles, helper slots, T of the sum-only tasks, T' of the diagonal tiles, claims
@@ -2032,6 +2164,7 @@ struct DataflowChol {
         C.nwg = which ? chain_wgB : chain_wg;
         C.ctr_slot = which ? 5 : 3; C.role_slot = which ? 6 : 4;
         C.trace_potf2 = env_int("DBAT_HIP_DF_TRACE_POTF2", 0);
+        C.plist = d_plist;
         return C;
     }
     int chain_grid(int work, int wg) const { return std::max(std::min(grid, work + wg), wg + 1); }

@@ -200,6 +200,44 @@ int dbat_hip_debug_nd_stats(const dbat_hip_problem *prob, int32_t mode, double *
     API_CATCH
 }
 
+/* Host only (debug / CPU unit tests): the schedule of the factorisation in the compact layout on one rank, as the
+ * handle would build it for this problem (the plan's dissection, DBAT_HIP_DF_SUMS / DBAT_HIP_DF_MERGE honoured) -- see
+ * include/dbat_hip.h. */
+int dbat_hip_debug_df_schedule(const dbat_hip_problem *prob, int64_t *hdr, double *cand_us, int32_t *jobs, int64_t jobs_cap,
+                               int32_t *plist, int64_t plist_cap, uint64_t *rowbits, int64_t rowbits_cap) {
+    API_TRY
+    if (!prob || !hdr || !cand_us) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    Plan P;
+    if (!build_plan(*prob, P, false)) { g_err = P.err; return DBAT_HIP_EINVAL; }
+    if (P.shared_eo || P.nd.nparts > 1) { g_err = "df_schedule: the compact layout on one rank only"; return DBAT_HIP_EINVAL; }
+    DataflowChol D;
+    DataflowChol::Symbolic Y;
+    D.symbolic_permuted(P.nc, P.nIOu, P.cam_adj.data(), P.cam_adj_words, P.nd, Y);
+    DataflowChol::Sched H;
+    D.schedule_host(Y.rb, Y.col_owner, 0, H);
+    int64_t nlisted = 0;
+    for (const DfJob &j : D.h_tasks) nlisted += (j.mode & DF_LISTED) != 0;
+    const int64_t h[16] = {D.nT, D.W, D.ntasks, (int64_t)D.h_plist.size(), D.cand_taken, D.nparts, D.n_products, D.use_chain ? 1 : 0,
+                           D.nchain, nlisted, DF_LISTED, (int64_t)Y.rb.size(), 0, 0, 0, 0};
+    std::copy(h, h + 16, hdr);
+    std::copy(D.cand_us, D.cand_us + 4, cand_us);
+    if (jobs) {
+        if (jobs_cap < (int64_t)D.h_tasks.size() * 8) { g_err = "df_schedule: task buffer too small"; return DBAT_HIP_EINVAL; }
+        static_assert(sizeof(DfJob) == 8 * sizeof(int32_t), "DfJob is eight ints");
+        if (!D.h_tasks.empty()) memcpy(jobs, D.h_tasks.data(), D.h_tasks.size() * sizeof(DfJob));
+    }
+    if (plist) {
+        if (plist_cap < (int64_t)D.h_plist.size()) { g_err = "df_schedule: list buffer too small"; return DBAT_HIP_EINVAL; }
+        std::copy(D.h_plist.begin(), D.h_plist.end(), plist);
+    }
+    if (rowbits) {
+        if (rowbits_cap < (int64_t)Y.rb.size()) { g_err = "df_schedule: pattern buffer too small"; return DBAT_HIP_EINVAL; }
+        std::copy(Y.rb.begin(), Y.rb.end(), rowbits);
+    }
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
 /* Host evaluation of the per-observation model (debug / CPU unit tests of
  * model.hpp only; never used by the product path). */
 int dbat_hip_debug_model_eval_host(int32_t model, int32_t nK, int32_t nP, const double *EO6, const double *IO,

@@ -42,6 +42,7 @@ static const EnvSwitch kEnvSwitches[] = {
     {"DBAT_HIP_DF_CHUNK", false, "factorisation: products per helper task (default 32)"},
     {"DBAT_HIP_DF_CHAIN", false, "factorisation: 0 = diagonal tiles as ordinary tasks (no chain role), 1 = chain role whatever the pattern", "0|1"},
     {"DBAT_HIP_DF_MERGE", false, "factorisation: sums of the columns where two parts of the dissection meet cut into early and late pieces: 0 = never, 1 = wherever the chain role is on (default: where the simulated schedule is shorter)", "0|1"},
+    {"DBAT_HIP_DF_SUMS", false, "factorisation, compact tiles on one rank with the chain role on: a sum takes its products in the order the schedule's model expects their tiles to exist (a list fixed at plan time): 0 = never, 1 = always, 2 / 3 = every task a list in ascending / descending column order (control, tests) (default: where the simulated schedule is shorter)", "0|1|2|3"},
     {"DBAT_HIP_DF_CHAIN_WG", false, "factorisation: workgroups of the chain role at most (default 32)"},
     {"DBAT_HIP_DF_L2", false, "factorisation: 1 = finished tiles of the compact layout are read through the L2", "0|1"},
     {"DBAT_HIP_COV_DENSE", false, "posterior covariance: the dense inverse of the reduced system (rocsolver_dpotri) instead of the selected inversion"},

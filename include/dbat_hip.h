@@ -737,6 +737,24 @@ int32_t dbat_hip_quality_hull_cap(void);
  * with the kernel's own filter, order, chain scan and shoelace sum; for tests, never on the product path. */
 int  dbat_hip_debug_coverage_host(const dbat_hip_problem *prob, double *lo, double *hi, double *rad_max, int64_t *rad_ip,
                                   double *hull_area, int64_t *hull_start, int64_t *hull_ip);
+/* Host only, no GPU (debug / tests; never on the product path): the task list of the factorisation of the reduced
+ * system in the compact tile layout on one rank, as a handle would schedule it for this problem.  Product lists are made only
+ * where the chain role is on (the kernel without it walks none).
+ *   hdr[16]      { tile columns nT, 64-bit words W per row of the pattern, tasks, entries of the product lists, the
+ *                  candidate taken, partial-sum slots, tile products, chain role (0 | 1), diagonal tiles of the chain
+ *                  role, tasks with a product list, the bit of a task's mode that marks a listed task,
+ *                  (nT + 1) * W, 0 ... }
+ *   cand_us[4]   modelled time in microseconds of the candidate schedules: 0 every sum in column order, 1 the sums cut
+ *                where two parts of the dissection meet, 2 product lists, 3 lists and cut sums (< 0: not made)
+ *   jobs         [8 * tasks] i, k, jlo, jhi, part, np, mode, p per task in task order.  Its products are the columns
+ *                j in [jlo, jhi) with a tile in both tile rows i and k, in column order -- or, where mode has the
+ *                listed bit, the entries [jlo, jhi) of plist in that order
+ *   rowbits      [(nT + 1) * W] bit k of row i: tile (i, k) exists after fill (row nT: the right-hand side)
+ * jobs, plist and rowbits may be NULL (sizes from hdr first); a capacity that is too small is DBAT_HIP_EINVAL.
+ * DBAT_HIP_DF_SUMS and DBAT_HIP_DF_MERGE are honoured as by a handle. */
+int  dbat_hip_debug_df_schedule(const dbat_hip_problem *prob, int64_t *hdr, double *cand_us, int32_t *jobs,
+                                int64_t jobs_cap, int32_t *plist, int64_t plist_cap, uint64_t *rowbits,
+                                int64_t rowbits_cap);
 
 /* ---- robust estimation: iteratively reweighted least squares over the image points -------------------------------
  * For image point i (one IP column, two rows) at parameters x:
