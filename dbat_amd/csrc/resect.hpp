@@ -119,6 +119,40 @@ __host__ __device__ inline int rs_poses_3pt(const double X[3][3], const double d
     return np_;
 }
 
+// The reprojection error of a check point in twice the working precision.  Evaluated plainly, h = P [Q; 1] carries
+// a few eps of |R Q| + |t| and x = h0 / h2 - xn a few eps of |xn|: 1e-13 of a residual of 1e-3, and all of the residual
+// of a point the pose was solved from -- so the rms would be known to no better than that.  Error-free sums and
+// products (Knuth's TwoSum, the FMA product; Ogita, Rump & Oishi's Dot2) give (h0 - xn h2) / h2 to rounding whatever
+// its size.  No contraction in these: a sum that absorbed a product would not be the rounded sum TwoSum corrects.
+__host__ __device__ inline void rs_two_sum(double a, double b, double &s, double &e) {
+#pragma clang fp contract(off)
+    s = a + b;
+    const double bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+}
+__host__ __device__ inline void rs_two_prod(double a, double b, double &p, double &e) {
+#pragma clang fp contract(off)
+    p = a * b;
+    e = fma(a, b, -p);
+}
+// p0 Q[0] + p1 Q[1] + p2 Q[2] + t as the unevaluated sum hi + lo
+__host__ __device__ inline void rs_dot2(double p0, double p1, double p2, double t, const double *Q, double &hi, double &lo) {
+#pragma clang fp contract(off)
+    double s = t, c = 0, p, pe, se;
+    rs_two_prod(p0, Q[0], p, pe); rs_two_sum(s, p, s, se); c += pe + se;
+    rs_two_prod(p1, Q[1], p, pe); rs_two_sum(s, p, s, se); c += pe + se;
+    rs_two_prod(p2, Q[2], p, pe); rs_two_sum(s, p, s, se); c += pe + se;
+    rs_two_sum(s, c, hi, lo);
+}
+// ((h + hl) - xn (w + wl)) / (w + wl)
+__host__ __device__ inline double rs_resid(double h, double hl, double w, double wl, double xn) {
+#pragma clang fp contract(off)
+    double p, pe, s, se;
+    rs_two_prod(xn, w, p, pe);
+    rs_two_sum(h, -p, s, se);
+    return (s + ((se - pe) + (hl - xn * wl))) / (w + wl);
+}
+
 // One wave per camera.  pt_start[c] .. pt_start[c+1]: the camera's check points (X object coordinates,
 // xn normalised image coordinates); tri_start[c] .. tri_start[c+1]: its candidate triangles, three indices
 // local to the camera's point range each, in the order resect.m tries them.
@@ -152,10 +186,11 @@ __global__ __launch_bounds__(64) void k_resect(int n_images, const int64_t *__re
             double acc = 0;
             for (int64_t i = lane; i < npt; i += 64) {
                 const double *Q = X + 3 * (p0 + i);
-                const double h0 = sP[q][0] * Q[0] + sP[q][3] * Q[1] + sP[q][6] * Q[2] + sP[q][9];
-                const double h1 = sP[q][1] * Q[0] + sP[q][4] * Q[1] + sP[q][7] * Q[2] + sP[q][10];
-                const double h2 = sP[q][2] * Q[0] + sP[q][5] * Q[1] + sP[q][8] * Q[2] + sP[q][11];
-                const double e0 = h0 / h2 - xn[2 * (p0 + i)], e1 = h1 / h2 - xn[2 * (p0 + i) + 1];
+                double h0, h0l, h1, h1l, h2, h2l;
+                rs_dot2(sP[q][0], sP[q][3], sP[q][6], sP[q][9], Q, h0, h0l);
+                rs_dot2(sP[q][1], sP[q][4], sP[q][7], sP[q][10], Q, h1, h1l);
+                rs_dot2(sP[q][2], sP[q][5], sP[q][8], sP[q][11], Q, h2, h2l);
+                const double e0 = rs_resid(h0, h0l, h2, h2l, xn[2 * (p0 + i)]), e1 = rs_resid(h1, h1l, h2, h2l, xn[2 * (p0 + i) + 1]);
                 acc += e0 * e0 + e1 * e1;
             }
             for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);

@@ -379,7 +379,10 @@ int  dbat_hip_owned_mask(const dbat_hip_handle *h, uint8_t *mask);
  * points by forward intersection of their lens-corrected image rays with the IO / EO of x
  * (the OP part of x is not used).  OP [3*n_points] in: current values, out: intersected
  * points; skip[p] != 0 (may be NULL) leaves point p as it is; a point with fewer than two
- * rays becomes NaN.  Collective on a sharded handle. */
+ * rays -- one, or none at all -- becomes NaN.  Collective on a sharded handle: every point is
+ * intersected once, by the rank that owns it, from all its rays; one sum over the ranks of
+ * 4*n_points doubles (the points, and for each whether it has a ray at all) gives every rank
+ * the one-rank result. */
 int  dbat_hip_forwintersect(dbat_hip_handle *h, const double *x, const uint8_t *skip, double *OP);
 
 /* [s,rms,fail] = resect(s0, cams, cpId, n, v, chkId) (photogrammetry/resect.m:42-131) with the per-camera work on
@@ -393,7 +396,8 @@ int  dbat_hip_forwintersect(dbat_hip_handle *h, const double *x, const uint8_t *
  *   tri_start [n_images+1]  range of every camera's candidate triangles in tri
  *   tri       [3*total]     three indices into the camera's point range per triangle, in trial order
  *   P         [12*n_images] out: best 3 x 4 camera matrix (column-major), NaN if the camera has no pose
- *   rms       [n_images]    out: its rms error, Inf if none
+ *   rms       [n_images]    out: its rms error, Inf if none; the residuals are evaluated in twice the working
+ *                           precision, so it is the rms of the returned P to rounding whatever its size
  * Returns DBAT_HIP_EDEVICE without a HIP device (no CPU path). */
 int  dbat_hip_resect(int32_t device, int32_t n_images, const int64_t *pt_start, const double *X, const double *xn,
                      const int64_t *tri_start, const int32_t *tri, double *P, double *rms);
