@@ -210,6 +210,7 @@ SYMBOLS = {
     'dbat_hip_set_obs_weights': (C.c_int, [_H, _dp]),
     'dbat_hip_solve_robust': (C.c_int, [_H, C.POINTER(Options), C.POINTER(RobustOptions), _dp, C.POINTER(Result),
                                         _dp, _dp, _dp, _dp, C.POINTER(RobustResult), _dp]),
+    'dbat_hip_debug_robust_from_s': (C.c_int, [_H, _dp, C.POINTER(RobustOptions), _dp, _dp, _dp, _dp, _bp]),
 }
 DEBUG_SYMBOLS = {
     'dbat_hip_debug_plan_digest': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_uint64), C.c_int32, C.c_char_p, C.c_int32]),
@@ -750,6 +751,20 @@ class Handle:
         if om.size != int(self.prob.n_obs):
             raise ValueError('set_obs_weights: %d values for %d image points' % (om.size, int(self.prob.n_obs)))
         check(self.lib.dbat_hip_set_obs_weights(self.h, dptr(om)))
+
+    def debug_robust_from_s(self, s, ropt):
+        """The select, scale and weight half of a reweighting evaluation on the caller's s per IP column (debug,
+        dbat_hip_debug_robust_from_s; not applied): (omega, median, scale, max_change, owned) -- median NaN with the
+        a-priori scale, owned the mask of the IP columns this rank holds.  Collective on a sharded handle."""
+        s = np.ascontiguousarray(s, float).ravel()
+        no = int(self.prob.n_obs)
+        if s.size != no:
+            raise ValueError('debug_robust_from_s: %d values for %d image points' % (s.size, no))
+        om, own = np.zeros(max(no, 1)), np.zeros(max(no, 1), np.uint8)
+        med, sc, chg = C.c_double(), C.c_double(), C.c_double()
+        check(self.lib.dbat_hip_debug_robust_from_s(self.h, dptr(s), C.byref(ropt), dptr(om), C.byref(med), C.byref(sc),
+                                                    C.byref(chg), own.ctypes.data_as(_bp)))
+        return om[:no], med.value, sc.value, chg.value, own[:no].astype(bool)
 
     def solve_robust(self, x0, opt, ropt):
         """The IRLS outer loop (dbat_hip_solve_robust): (x, Result, res, damp, aux, T, RobustResult, omega) -- the

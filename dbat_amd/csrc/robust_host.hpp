@@ -121,20 +121,27 @@ static double robust_median(Core &c, RobustState &r) {
     memcpy(&a, &st[0], 8); memcpy(&b, &st[1], 8);
     return (a + b) / 2.0;
 }
-// One evaluation at zz (collective): s of every owned observation (rs_bits), the scale, omega' and max |omega' -
-// omega| over all ranks.  s_ip / omega_ip (device, [no], zero outside this rank's observations): optional.
-static void robust_eval(Core &c, RobustState &r, const double *zz, const dbat_hip_robust_options &ro, double *s_ip, double *omega_ip, double &scale, double &maxchg) {
+// First half of an evaluation: s of every owned observation at zz into rs_bits.  s_ip (device, [no], zero outside this
+// rank's observations): optional.
+static void robust_norms(Core &c, RobustState &r, const double *zz, double *s_ip) {
     const Plan &P = c.P;
     const int64_t nobs = c.nobs;
-    robust_scratch(c, r);
     HIPCHK(hipMemsetAsync(r.robust_r.p, 0, (size_t)2 * P.no * sizeof(double), c.stream));
     c.eval_f(zz, nullptr, r.robust_r.p);
     if (nobs > 0)
         c.launch<k_robust_norm>(dim3(robust_grid(c)), dim3(256), 0, nobs, (const int64_t *)c.o_row.p, (const double *)r.robust_r.p,
                                 (const double *)(r.robust_on ? r.o_w_base.p : (P.uniform_w ? nullptr : c.o_w.p)), (const int32_t *)c.o_cam.p, (const double *)c.cam_w.p, r.rs_bits.p, s_ip);
+}
+// Second half (collective), from the bit patterns in rs_bits: the median of s over all ranks (NaN with the a-priori
+// scale, which selects nothing), the scale, omega' and max |omega' - omega| over all ranks.  omega_ip as s_ip above.
+static void robust_from_bits(Core &c, RobustState &r, const dbat_hip_robust_options &ro, double *omega_ip, double &median, double &scale, double &maxchg) {
+    const Plan &P = c.P;
+    const int64_t nobs = c.nobs;
     scale = 1.0;
+    median = std::nan("");
     if (ro.scale == DBAT_HIP_SCALE_MAD && P.no > 0) {
-        scale = robust_median(c, r) / ROBUST_MAD_C;
+        median = robust_median(c, r);
+        scale = median / ROBUST_MAD_C;
         if (scale == 0.0) scale = 1.0;
     }
     HIPCHK(hipMemsetAsync(r.rmax.p, 0, sizeof(unsigned long long), c.stream));
@@ -146,6 +153,13 @@ static void robust_eval(Core &c, RobustState &r, const double *zz, const dbat_hi
     HIPCHK(hipStreamSynchronize(c.stream));
     memcpy(&maxchg, &mb, 8);
     maxchg = max_over_ranks(c, r, maxchg);
+}
+// One evaluation at zz (collective): both halves.
+static void robust_eval(Core &c, RobustState &r, const double *zz, const dbat_hip_robust_options &ro, double *s_ip, double *omega_ip, double &scale, double &maxchg) {
+    robust_scratch(c, r);
+    robust_norms(c, r, zz, s_ip);
+    double median;
+    robust_from_bits(c, r, ro, omega_ip, median, scale, maxchg);
 }
 // apply the omega' of the last evaluation (same scale and loss)
 static void robust_apply_eval(Core &c, RobustState &r, const dbat_hip_robust_options &ro, double scale) {
@@ -287,6 +301,51 @@ int dbat_hip_solve_robust(dbat_hip_handle *h, const dbat_hip_options *opt, const
         rr->inner_iters[rr->outer++] = result->iters;
     }
     if (omega_out) robust_omega_ip(c, r, omega_out);
+    return DBAT_HIP_OK;
+    API_CATCH
+}
+
+/* Debug / tests: the second half of a reweighting evaluation (select, scale, weights, largest change) on the caller's
+ * s instead of the residuals' (include/dbat_hip.h).  The host only places the bit patterns of this rank's observations
+ * in rs_bits, in processing order; everything after that is the code of a solve. */
+int dbat_hip_debug_robust_from_s(dbat_hip_handle *h, const double *s_ip, const dbat_hip_robust_options *ropt,
+                                 double *omega_ip, double *median, double *scale, double *max_change, uint8_t *owned) {
+    API_TRY
+    if (!h || !s_ip || !scale || !max_change) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
+    if (const char *e = robust_args_error(ropt)) { g_err = e; return DBAT_HIP_EINVAL; }
+    Core &c = *h->core;
+    const Plan &P = c.P;
+    for (int64_t i = 0; i < P.no; ++i)
+        if (!std::isfinite(s_ip[i]) || std::signbit(s_ip[i])) {
+            g_err = "dbat_hip_debug_robust_from_s: s_ip[" + std::to_string(i) + "] is not finite with the sign bit clear";
+            return DBAT_HIP_EINVAL;
+        }
+    DeviceGuard dev_guard(c.device);
+    RobustState &r = built_once(h->rob);
+    robust_scratch(c, r);
+    if (c.nobs > 0) {           // processing order of this rank's observations
+        std::vector<uint64_t> bits((size_t)c.nobs);
+        for (int64_t k = 0; k < c.nobs; ++k) memcpy(&bits[k], &s_ip[P.o_row[k]], 8);
+        HIPCHK(hipMemcpy(r.rs_bits.p, bits.data(), bits.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    DevBuf<double> om;
+    if (omega_ip) {
+        om.alloc((size_t)std::max<int64_t>(P.no, 1));
+        HIPCHK(hipMemsetAsync(om.p, 0, (size_t)P.no * sizeof(double), c.stream));
+    }
+    double med = 0.0, sc = 1.0, chg = 0.0;
+    robust_from_bits(c, r, *ropt, om.p, med, sc, chg);
+    if (omega_ip) {
+        if (c.multi()) c.do_allreduce(om.p, P.no);
+        HIPCHK(hipMemcpyAsync(omega_ip, om.p, (size_t)P.no * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        HIPCHK(hipStreamSynchronize(c.stream));
+    }
+    if (median) *median = med;
+    *scale = sc; *max_change = chg;
+    if (owned) {
+        std::fill(owned, owned + P.no, (uint8_t)0);
+        for (int64_t k = 0; k < c.nobs; ++k) owned[P.o_row[k]] = 1;
+    }
     return DBAT_HIP_OK;
     API_CATCH
 }

@@ -816,6 +816,22 @@ int  dbat_hip_solve_robust(dbat_hip_handle *h, const dbat_hip_options *opt, cons
                            double *x, dbat_hip_result *result, double *res, double *damp, double *aux, double *trace,
                            dbat_hip_robust_result *rr, double *omega_out);
 
+/* Debug / tests, never on the product path: the second half of a reweighting evaluation on the caller's s instead of
+ * the residuals' -- the exact median by radix select, the scale (median / sqrt(2 ln 2), 1 if that is 0; 1 with
+ * DBAT_HIP_SCALE_APRIORI), the weights and the largest weight change, by the kernels and host code of
+ * dbat_hip_solve_robust.  s_ip [n_obs] in IP column order: every value finite with the sign bit clear (so -0.0 is
+ * refused), else DBAT_HIP_EINVAL naming the column, before anything is launched.  The host places the bit patterns of
+ * this rank's observations in processing order; nothing else differs from a solve, and nothing is applied to the
+ * handle.
+ *   omega_ip   [n_obs] or NULL: omega' in IP column order, complete on every rank
+ *   median     or NULL: the median of s over all ranks (NaN with DBAT_HIP_SCALE_APRIORI, which selects nothing)
+ *   scale, max_change   the scale; max |omega' - omega| over all ranks, omega the factors the handle carries
+ *              (dbat_hip_set_obs_weights or a robust solve; 1 on a handle that was never promoted)
+ *   owned      [n_obs] or NULL: 1 where this rank holds the IP column
+ * Collective on a sharded handle: every rank passes the same s_ip and the same set of non-NULL outputs. */
+int  dbat_hip_debug_robust_from_s(dbat_hip_handle *h, const double *s_ip, const dbat_hip_robust_options *ropt,
+                                  double *omega_ip, double *median, double *scale, double *max_change, uint8_t *owned);
+
 #ifdef __cplusplus
 }
 #endif

@@ -661,6 +661,8 @@ def test_mad_median_of_rounding_level_residuals(hip, odd):
     works in its low passes and the "1 if 0" rule can apply.  Whichever branch the returned s dictates is asserted.
     On the MI355X both counts took the non-zero branch: median(s) = 1.563e-13 for 1800 and for 1799 image points, no s
     exactly 0 (the device's closed-form projection leaves rounding in every row), scale = median / sqrt(2 ln 2) exactly.
+    The zero branch is taken on the device by test_robust_select_gpu.py::test_median_and_scale_are_exact (all-zero,
+    zeros-majority, zeros-half), which feeds the select crafted values instead of residuals.
     """
     from test_robust_gpu import _drop_last_ip
     s = synth_struct('tiny', 'plain')[0]
