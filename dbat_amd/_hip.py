@@ -184,6 +184,10 @@ SYMBOLS = {
     'dbat_hip_default_pair_options': (C.c_int, [C.POINTER(PairOptions)]),
     'dbat_hip_pairadjust': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, _bp, _dp, _dp, C.c_int32,
                                       C.POINTER(PairOptions), _dp, _dp, _bp, _dp, _ip, _dp, _dp]),
+    'dbat_hip_resect_ransac': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, _bp, C.POINTER(C.c_int64), _ip, _dp,
+                                         _dp, _ip, _bp, _dp]),
+    'dbat_hip_poseadjust': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, _bp, _dp, C.POINTER(PairOptions), _dp,
+                                      _bp, _dp, _ip, _dp, _dp]),
     'dbat_hip_bench_step': (C.c_int, [_H, C.c_double, C.c_int32, _dp]),
     'dbat_hip_structure_key': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_uint64)]),
     'dbat_hip_handle_key': (C.c_int, [_H, C.POINTER(C.c_uint64)]),
@@ -229,6 +233,8 @@ DEBUG_SYMBOLS = {
     'dbat_hip_debug_relorient_timing': (C.c_int, [C.c_int32]),
     'dbat_hip_debug_pairadjust_ms': (C.c_int, [_dp]),
     'dbat_hip_debug_pairadjust_timing': (C.c_int, [C.c_int32]),
+    'dbat_hip_debug_resect_robust_ms': (C.c_int, [_dp]),
+    'dbat_hip_debug_resect_robust_timing': (C.c_int, [C.c_int32]),
 }
 
 _lib = None
@@ -1055,6 +1061,76 @@ def pairadjust_ms():
     ms = np.zeros(1)
     check(load().dbat_hip_debug_pairadjust_ms(dptr(ms)))
     return float(ms[0])
+
+
+def resect_ransac(pt_start, X, xn, smp_start, samples, thr2, use=None, device=0):
+    """dbat_hip_resect_ransac over the cameras pt_start[i] .. pt_start[i + 1] of the columns of X (3-by-total) and xn
+    (2-by-total) with the samples smp_start[i] .. smp_start[i + 1] of the rows of samples (three indices local to the
+    camera each), the thresholds thr2 (one per camera) and the optional mask use (total booleans):
+    dict(P (n, 3, 4), stats (n, 4: count, sample, root, poses scored), inlier (total), ssq (n))."""
+    lib = load()
+    ps, ss = np.ascontiguousarray(pt_start, np.int64), np.ascontiguousarray(smp_start, np.int64)
+    n = len(ps) - 1
+    X, xn = np.asarray(X, float), np.asarray(xn, float)
+    smp = np.ascontiguousarray(np.asarray(samples, np.int32).reshape(-1, 3))
+    t2 = np.ascontiguousarray(np.broadcast_to(np.asarray(thr2, float), (max(n, 0),)))
+    if n < 0 or len(ss) != n + 1 or X.ndim != 2 or X.shape[0] != 3 or xn.shape != (2, X.shape[1]) or X.shape[1] != ps[-1] or smp.shape[0] != ss[-1]:
+        raise ValueError('resect_ransac: X must be 3-by-total, xn 2-by-total and samples k-by-3, total and k the ends of the last ranges')
+    total = X.shape[1]
+    Xf, xf = _f64(X), _f64(xn)
+    u = None if use is None else np.ascontiguousarray(np.broadcast_to(np.asarray(use, bool), (total,))).view(np.uint8)
+    P, st, ssq = np.zeros(12 * max(n, 1)), np.zeros(4 * max(n, 1), np.int32), np.zeros(max(n, 1))
+    inl = np.zeros(max(total, 1), np.uint8)
+    i64p = C.POINTER(C.c_int64)
+    check(lib.dbat_hip_resect_ransac(int(device), n, ps.ctypes.data_as(i64p), dptr(Xf), dptr(xf), None if u is None else u.ctypes.data_as(_bp),
+                                     ss.ctypes.data_as(i64p), smp.ctypes.data_as(_ip), dptr(t2), dptr(P), st.ctypes.data_as(_ip),
+                                     inl.ctypes.data_as(_bp), dptr(ssq)))
+    return dict(P=P[:12 * n].reshape(n, 4, 3).transpose(0, 2, 1), stats=st[:4 * n].reshape(n, 4), inlier=inl[:total].astype(bool), ssq=ssq[:n])
+
+
+def poseadjust(pt_start, X, xn, P, use=None, w=None, max_iter=20, conv_tol=1e-6, min_angle=0.0, residuals=False, device=0):
+    """dbat_hip_poseadjust over the cameras pt_start[i] .. pt_start[i + 1] of the columns of X (3-by-total) and xn
+    (2-by-total), from the start poses P (n, 3, 4: [R | -R C]); use (total booleans) and the weights w (2-by-total, or
+    anything that broadcasts to it) are optional.  Nothing given is changed.  Returns dict(P (n, 3, 4), used (total), f0,
+    f, sigma0, lam (n), code, iters, trials, n_used (n), Q (n, 6, 6: centre, then rotation vector), res (2, total; None
+    unless residuals))."""
+    lib = load()
+    ps = np.ascontiguousarray(pt_start, np.int64)
+    n = len(ps) - 1
+    X, xn = np.asarray(X, float), np.asarray(xn, float)
+    P = np.asarray(P, float).reshape(-1, 3, 4)
+    if n < 0 or X.ndim != 2 or X.shape[0] != 3 or xn.shape != (2, X.shape[1]) or X.shape[1] != ps[-1] or P.shape[0] != n:
+        raise ValueError('poseadjust: X must be 3-by-total, xn 2-by-total, total the end of the last range, and P one 3-by-4 per camera')
+    total = X.shape[1]
+    Xf, xf = _f64(X), _f64(xn)
+    wt = None if w is None else _f64(np.broadcast_to(np.asarray(w, float), (2, total)))
+    u = None if use is None else np.ascontiguousarray(np.broadcast_to(np.asarray(use, bool), (total,))).view(np.uint8)
+    Pf = np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(-1).copy()
+    Pf = np.concatenate([Pf, np.zeros(12)]) if n == 0 else Pf
+    used, ds, ist, Q = np.zeros(max(total, 1), np.uint8), np.zeros(4 * max(n, 1)), np.zeros(4 * max(n, 1), np.int32), np.zeros(36 * max(n, 1))
+    res = np.zeros(2 * max(total, 1)) if residuals else None
+    opt = PairOptions(int(max_iter), float(conv_tol), float(min_angle))
+    check(lib.dbat_hip_poseadjust(int(device), n, ps.ctypes.data_as(C.POINTER(C.c_int64)), dptr(Xf), dptr(xf),
+                                  None if u is None else u.ctypes.data_as(_bp), dptr(wt), C.byref(opt), dptr(Pf),
+                                  used.ctypes.data_as(_bp), dptr(ds), ist.ctypes.data_as(_ip), dptr(Q), dptr(res)))
+    ds, ist = ds[:4 * n].reshape(n, 4), ist[:4 * n].reshape(n, 4)
+    return dict(P=Pf[:12 * n].reshape(n, 4, 3).transpose(0, 2, 1), used=used[:total].astype(bool), f0=ds[:, 0].copy(), f=ds[:, 1].copy(),
+                sigma0=ds[:, 2].copy(), lam=ds[:, 3].copy(), code=ist[:, 0].copy(), iters=ist[:, 1].copy(), trials=ist[:, 2].copy(),
+                n_used=ist[:, 3].copy(), Q=Q[:36 * n].reshape(n, 6, 6).transpose(0, 2, 1),
+                res=None if res is None else res[:2 * total].reshape(total, 2).T)
+
+
+def resect_robust_timing(on=True):
+    """Device events around the kernels of resect_ransac / poseadjust calls on this thread (debug; off by default)."""
+    check(load().dbat_hip_debug_resect_robust_timing(int(bool(on))))
+
+
+def resect_robust_ms():
+    """Device-event milliseconds of the kernels of the last resect_ransac and poseadjust calls on this thread, after
+    resect_robust_timing(True) (debug)."""
+    ms = np.zeros(2)
+    check(load().dbat_hip_debug_resect_robust_ms(dptr(ms)))
+    return dict(ransac=float(ms[0]), adjust=float(ms[1]))
 
 
 def rigidalign(X, Y, scale=False, use=None, resid=False, device=0):

@@ -33,6 +33,8 @@
 #include "align.hpp"
 #include "relorient.hpp"
 #include "pairadjust.hpp"
+#include "resect_ransac.hpp"
+#include "poseadjust.hpp"
 
 namespace dbat {
 
@@ -2008,3 +2010,4 @@ int dbat_hip_info(const dbat_hip_handle *h, int64_t *info) {
 #include "align_host.hpp"         // the network transforms take no handle
 #include "relorient_host.hpp"     // nor does the relative orientation
 #include "pairadjust_host.hpp"    // nor its least-squares refinement
+#include "poseadjust_host.hpp"    // nor the robust resection

@@ -13,6 +13,10 @@ control points and forward intersection of the object points, on
   refine_pairs, relorient(refine=True) -> dbat_hip_pairadjust (csrc/pairadjust.hpp k_pairadjust): the least-squares
                    relative orientation of the pairs, one workgroup per pair; the reference refines a pair only through
                    bundle.m on a two-image project
+  resect_robust, draw_triples -> dbat_hip_resect_ransac (csrc/resect_ransac.hpp k_resect_ransac: one workgroup per camera, a
+                   RANSAC over triples of control points scored by inlier count) and dbat_hip_poseadjust
+                   (csrc/poseadjust.hpp k_poseadjust: the least-squares space resection on the winner's inliers, one wave
+                   per camera); the reference has neither
   largesttriangle (misc/largesttriangle.m:16-41), derotmat3d (photogrammetry/derotmat3d.m:17-19), rotmat3d (its inverse),
   lenscorr1 (bundle/cammodel/pm_multilenscorr1.m:45-69 + pm_lens1.m:36-72), cleareo, clearop (misc/)
 
@@ -397,6 +401,157 @@ def relorient(s0, i, j, n_hyp=512, thr_px=3.0, seed=0, device=0, refine=False, m
     f = info['in_front']
     s.OP.val[:, info['pts'][f]] = X[:, f]
     return s, True, info
+
+
+# ---- robust resection --------------------------------------------------------------------------------------------------
+
+def draw_triples(n, n_hyp, rng):
+    """n_hyp rows of three distinct indices below n >= 3 from the generator rng, by the rule of draw_samples: rows with a
+    repeated index are drawn again until none is left (n < 16: the head of a permutation per row)."""
+    n, n_hyp = int(n), int(n_hyp)
+    if n < 3:
+        raise ValueError('draw_triples: fewer than three points')
+    if n < 16:
+        return np.array([rng.permutation(n)[:3] for _ in range(n_hyp)], np.int32).reshape(n_hyp, 3)
+    S = rng.integers(0, n, (n_hyp, 3))
+    while True:
+        srt = np.sort(S, 1)
+        bad = np.flatnonzero(np.any(srt[:, 1:] == srt[:, :-1], 1))
+        if bad.size == 0:
+            return S.astype(np.int32)
+        S[bad] = rng.integers(0, n, (bad.size, 3))
+
+
+def camera_points(s, ci, cpId=None, xy=None):
+    """(rows, xn, w) of camera ci: the columns of IP of its image points whose object point has an id in cpId (default:
+    every object point) and finite coordinates, their lens-corrected coordinates normalised as resect() does (K \\ [x; y; 1]
+    with -f), and their weights in these units as pair_weights computes them, |f| / (pxSize[axis] IP.std[axis, column])."""
+    xy = lenscorr1(s) if xy is None else xy
+    rows = np.flatnonzero(s.IP.cam == ci)
+    keep = np.all(np.isfinite(s.OP.val[:, s.IP.pt[rows]]), 0)
+    if cpId is not None:
+        keep &= np.isin(s.OP.id[s.IP.pt[rows]], cpId)
+    rows = rows[keep]
+    IO = s.IO.val[:, ci]
+    xn = np.stack([(xy[0, rows] - IO[1]) / -IO[0], (xy[1, rows] - IO[2]) / -IO[0]])
+    px = np.asarray(s.IO.sensor.pxSize, float)[:, ci]
+    if getattr(s.IO.sensor, 'samePxSize', False):
+        px = np.array([px[0], px[0]])
+    return rows, xn, abs(IO[0]) / (px[:, None] * np.asarray(s.IP.std, float)[:, rows])
+
+
+def resect_robust(s0, cams='all', cpId=None, n_hyp=256, thr_px=3.0, seed=0, refine=True, reselect=0, max_iter=20, conv_tol=1e-6,
+                  device=0):
+    """Robust spatial resection of the listed camera stations: (s, info, fail).  Per camera the image points of the object
+    points with ids cpId (default: every object point with finite coordinates) are lens-corrected and normalised as
+    resect() does, n_hyp triples are drawn with np.random.default_rng(seed) (draw_triples, camera after camera from the
+    one generator), and one device call (dbat_hip_resect_ransac) solves every triple and returns the pose with the most
+    points within thr_px pixels -- thr_px mean(pxSize) / |f| in normalised units.  With refine the inliers of every
+    winner go through the least-squares resection (dbat_hip_poseadjust, all cameras in one call) with the weights of
+    IP.std; every one of `reselect` rounds then thresholds the residuals of all the camera's points at the refined pose
+    again and refines on the new inliers, where they are not fewer and the adjustment converges.  In s -- a copy -- the EO
+    centre and omega, phi, kappa (derotmat3d) of the cameras come from the pose, as resect() writes them.  info[k], for
+    camera cams[k]:
+      ids, inlier, count   the ids of the object points considered, the mask of the inliers over them, their number
+      sample               the winning triple (indices into ids), None without a winner
+      P                    the 3-by-4 pose [R | -R C]
+      sigma0, Q, cov       of the refinement: sqrt(f / (2 count - 6)), the 6-by-6 cofactor matrix of (centre, rotation
+                           vector) and sigma0^2 Q; NaN without refine
+      code, iters          of the refinement (0 converged / 1 max_iter / 2 no step / 3 singular); 0 without refine
+      rms_px               the rms over the inliers of the residual in pixels
+    A camera without a winner -- fewer than four points agree with any sample -- gets NaN in EO and code -1, and fail is
+    True.  The lens correction is applied to the measurements (lenscorr1), not to the projections, as in refine_pairs."""
+    from . import _hip
+    from .dbatstruct import copy_struct
+    s = copy_struct(s0)
+    nc = s0.EO.val.shape[1]
+    cams = list(range(nc)) if isinstance(cams, str) and cams == 'all' else [int(c) for c in cams]
+    cpId = None if cpId is None else np.asarray(cpId)
+    xy = lenscorr1(s0)
+    rng = np.random.default_rng(seed)
+    pt_start, smp_start, Xs, xs, ws, smps, thr, ids = [0], [0], [], [], [], [], [], []
+    for ci in cams:
+        rows, xn, w = camera_points(s0, ci, cpId, xy)
+        ids.append(s0.OP.id[s0.IP.pt[rows]])
+        Xs.append(s0.OP.val[:, s0.IP.pt[rows]]); xs.append(xn); ws.append(w)
+        smps.append(draw_triples(rows.size, n_hyp, rng) if rows.size >= 3 else np.zeros((0, 3), np.int32))
+        thr.append(float(thr_px) * np.mean(s0.IO.sensor.pxSize[:, ci]) / abs(s0.IO.val[0, ci]))
+        pt_start.append(pt_start[-1] + rows.size)
+        smp_start.append(smp_start[-1] + smps[-1].shape[0])
+    if not cams:
+        return s, [], False
+    X, xn, w, thr = np.concatenate(Xs, 1), np.concatenate(xs, 1), np.concatenate(ws, 1), np.array(thr)
+    r = _hip.resect_ransac(pt_start, X, xn, smp_start, np.concatenate(smps, 0), thr ** 2, device=device)
+    nan = np.nan
+    info = []
+    for k in range(len(cams)):
+        sl = slice(pt_start[k], pt_start[k + 1])
+        st = r['stats'][k]
+        won = st[1] >= 0
+        info.append(dict(ids=ids[k], inlier=r['inlier'][sl].copy(), count=int(st[0]), sample=smps[k][st[1]].copy() if won else None,
+                         P=r['P'][k].copy(), sigma0=nan, Q=np.full((6, 6), nan), cov=np.full((6, 6), nan), code=0 if won else -1, iters=0,
+                         rms_px=float(np.sqrt(r['ssq'][k] / st[0])) / thr[k] * float(thr_px) if won else nan))
+    todo = [k for k in range(len(cams)) if info[k]['code'] == 0]
+
+    def adjust(which):
+        """poseadjust of the cameras `which` on their current inliers, from their current poses."""
+        ps = np.cumsum([0] + [pt_start[k + 1] - pt_start[k] for k in which])
+        cat = lambda a: np.concatenate([a[:, pt_start[k]:pt_start[k + 1]] for k in which], 1)
+        a = _hip.poseadjust(ps, cat(X), cat(xn), np.stack([info[k]['P'] for k in which]), use=np.concatenate([info[k]['inlier'] for k in which]),
+                            w=cat(w), max_iter=max_iter, conv_tol=conv_tol, residuals=True, device=device)
+        return a, ps
+
+    def take(k, a, m, sl):
+        """The refinement a[m] becomes the result of camera k."""
+        f = info[k]
+        wk = w[:, pt_start[k]:pt_start[k + 1]]
+        s0k = float(a['sigma0'][m])
+        e2 = np.sum((a['res'][:, sl] / wk) ** 2, 0)[a['used'][sl]]
+        f.update(P=a['P'][m].copy(), inlier=a['used'][sl].copy(), count=int(a['n_used'][m]), sigma0=s0k, Q=a['Q'][m].copy(),
+                 cov=s0k * s0k * a['Q'][m], code=int(a['code'][m]), iters=int(a['iters'][m]),
+                 rms_px=float(np.sqrt(np.mean(e2))) / thr[k] * float(thr_px))
+        f['res'] = a['res'][:, sl].copy()
+
+    if refine and todo:
+        a, ps = adjust(todo)
+        for m, k in enumerate(todo):
+            if a['code'][m] != 4:
+                take(k, a, m, slice(ps[m], ps[m + 1]))
+        for _ in range(int(reselect)):
+            again = []
+            for k in todo:
+                f = info[k]
+                if 'res' not in f:
+                    continue
+                sl = slice(pt_start[k], pt_start[k + 1])
+                e2 = np.sum((f['res'] / w[:, sl]) ** 2, 0)
+                front = f['P'][2, :3] @ X[:, sl] + f['P'][2, 3] < 0
+                mask = front & (e2 <= thr[k] ** 2)
+                if mask.sum() >= f['count'] and not np.array_equal(mask, f['inlier']):
+                    f['_kept'] = (f['inlier'], f['count'])
+                    f['inlier'] = mask
+                    again.append(k)
+            if not again:
+                break
+            a, ps = adjust(again)
+            for m, k in enumerate(again):
+                kept = info[k].pop('_kept')
+                if a['code'][m] == 0 and a['n_used'][m] >= kept[1]:
+                    take(k, a, m, slice(ps[m], ps[m + 1]))
+                else:
+                    info[k]['inlier'] = kept[0]
+    fail = False
+    for k, ci in enumerate(cams):
+        f = info[k]
+        f.pop('res', None)
+        if f['code'] >= 0:
+            R, t = f['P'][:, :3], f['P'][:, 3]
+            s.EO.val[:3, ci] = -R.T @ t
+            s.EO.val[3:6, ci] = derotmat3d(R)
+        else:
+            fail = True
+            s.EO.val[:6, ci] = np.nan
+    return s, info, fail
 
 
 resect_hip = resect                   # (names of rounds 2-3)

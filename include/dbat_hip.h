@@ -565,6 +565,81 @@ int  dbat_hip_pairadjust(int32_t device, int32_t n_pairs, const int64_t *pt_star
                          const dbat_hip_pair_options *opt, double *P2, double *X, uint8_t *used, double *dstat,
                          int32_t *istat, double *Q, double *res);
 
+/* ---- robust resection (additive to ABI 5; csrc/resect_ransac.hpp, csrc/poseadjust.hpp) -------- */
+
+/* Spatial resection of n_images cameras by a RANSAC over triples of control points, in one call.  The reference has no
+ * counterpart: resect.m:42-131 tries the largest triangles and keeps the pose of smallest rms over all check points, so
+ * that one wrong control point decides the answer (dbat_hip_resect above keeps that behaviour).  No handle: the inputs
+ * are what resect.m has after its MATLAB-side preparation.
+ *   pt_start  [n_images+1]  range of every camera's points in X / xn; a camera may be empty
+ *   X         [3*total]     object coordinates, per camera
+ *   xn        [2*total]     lens-corrected, normalised image coordinates K \ [x; y; 1] with -f: the cameras look along
+ *                           -z, and a point is in front where the third row of P [X; 1] is negative
+ *   use       [total]       or NULL (all): the points that may be sampled and counted
+ *   smp_start [n_images+1]  range of every camera's samples in smp
+ *   smp       [3*total]     three distinct indices into the camera's point range per sample: drawn by the caller, so the
+ *                           call is deterministic
+ *   thr2      [n_images]    inlier threshold on the squared residual, in normalised units
+ *   P         [12*n_images] out: the winning 3 x 4 camera matrix (column-major), NaN if the camera has no winner
+ *   stats     [4*n_images]  out: the inlier count, the winning sample (local to the camera) and root (the index among
+ *                           the poses of its sample, in the order rs_poses_3pt returns them), the number of poses scored;
+ *                           count 0 and sample and root -1 without a winner
+ *   inlier    [total]       out: 1 where the point is an inlier of the returned P; all zero without a winner
+ *   ssq       [n_images]    out: the sum of e0^2 + e1^2 over the inliers; 0 without a winner
+ * One workgroup per camera; a lane solves one sample by the three-point resection of pm_resect_3pt.m:27-147 (up to four
+ * poses) and scores its poses against every point of the camera.  A point is an inlier of a pose if use is set, it is in
+ * front, and e0^2 + e1^2 <= thr2 with e = pi(P [X; 1]) - xn evaluated in twice the working precision, as dbat_hip_resect
+ * evaluates its rms.  The winner has the highest count; of equal counts the lowest (sample, root) wins; it needs at least
+ * four inliers (three is what every sample gets from itself).  A sample with a point that may not be used, with collinear
+ * points or without a real root scores nothing.  Counts are integers and the winner is one integer maximum: no
+ * floating-point atomics, two calls give the same bits, and a camera gives the same bits alone and in a batch.
+ * DBAT_HIP_EINVAL, before any device call: a point that may be used and is not finite; a sample index out of range or
+ * repeated inside its sample; thr2 not positive and finite; ranges that do not ascend from 0; 2^29 points or 2^31 samples
+ * and more in one camera.  Then DBAT_HIP_EDEVICE without a HIP device (no CPU path). */
+int  dbat_hip_resect_ransac(int32_t device, int32_t n_images, const int64_t *pt_start, const double *X, const double *xn,
+                            const uint8_t *use, const int64_t *smp_start, const int32_t *smp, const double *thr2, double *P,
+                            int32_t *stats, uint8_t *inlier, double *ssq);
+
+/* Least-squares space resection of n_images cameras in one call: the pose of every camera from its control points, with
+ * sigma0 and the cofactor matrix.  No handle, no plan; one wave per camera runs the whole damped loop.  The reference has
+ * no counterpart: it reaches this pose only through bundle.m on a one-camera project with every object point fixed.
+ *   pt_start  [n_images+1]  range of every camera's points; a camera may be empty
+ *   X, xn                   as dbat_hip_resect_ransac
+ *   use       [total]       or NULL (all): points that may be used
+ *   w         [2*total]     or NULL (ones): weights per coordinate, the reciprocal standard deviations in normalised units
+ *   opt                     max_iter and conv_tol of dbat_hip_pair_options, with its defaults; min_angle must be 0
+ *   P         [12*n_images] in/out: [R | -R C], column-major 3 x 4
+ *   used      [total]       out: the points used, chosen once at the start pose: use is set and the point is in front
+ *   dstat     [4*n_images]  out: the objective at the start, the objective, sigma0, lambda
+ *   istat     [4*n_images]  out: code, iterations (accepted steps), trials, n (the points used)
+ *   Q         [36*n_images] out: cofactor matrix, 6 x 6 column-major, of (c, a), centre first: the inverse of the undamped
+ *                           normal matrix at the returned values.  The covariance is sigma0^2 Q
+ *   res       [2*total]     out, or NULL: weighted residuals at the returned pose of every finite point, used or not (a
+ *                           caller can threshold them and call again); zero where they are not finite, and for a
+ *                           camera that ends with code 4
+ * Residuals: w (pi(R (X - C)) - xn), pi(Y) = Y(1:2) / Y(3); f is the sum of their squares over the n used points.  A step
+ * is C <- C + c, R <- exp([a]x) R: six unknowns.  The damping loop is that of dbat_hip_pairadjust point for point:
+ * Levenberg-Marquardt with Marquardt's scaling (lambda diag N), lambda from 1e-3, lambda <- max(lambda / 10, 1e-12) on an
+ * accepted trial, 10 lambda on a rejected one (the same linearisation is solved again), the end above 1e8; a trial is
+ * accepted if its objective is finite and smaller and every used point is still in front; every trial tests for the end
+ * first: q <= conv_tol^2 f with q = -g' delta, or f <= 1e-24 * 2 n.
+ * The normal equations are float64.  The objective of the accept test is formed and summed in pairs of doubles, and R is
+ * such a pair kept orthonormal, for the reason given at dbat_hip_pairadjust; the returned f and R are the high words.
+ * Object coordinates and the centre are taken relative to the camera's first used point before anything is multiplied:
+ * coordinates of 1e6 m keep their digits.
+ * Codes: 0 converged; 1 max_iter steps done; 2 no acceptable step before lambda > 1e8; 3 converged, but the undamped
+ * matrix has a Cholesky pivot <= 1e-10 of its diagonal entry: Q is NaN; 4 fewer than three points used: P is returned as
+ * given, dstat is NaN but for lambda, Q is NaN.  sigma0 = sqrt(f / (2 n - 6)), NaN for n = 3.  Q is NaN for every singular
+ * end, whatever the code.  Nothing else returned is ever non-finite.  The sums have a fixed shape and there are no atomics:
+ * two calls give the same bits, and a camera gives the same bits alone and in a batch.
+ * DBAT_HIP_EINVAL, before any device call: a point that may be used, a weight or a P that is not finite; a weight <= 0;
+ * an R with |R'R - I| > 1e-6 or det R < 0; a pt_start that does not ascend from 0; max_iter outside 1 .. 200;
+ * conv_tol <= 0; min_angle != 0.  Then DBAT_HIP_EDEVICE without a HIP device (no CPU path).  What the data of one camera
+ * cause -- too few points, no convergence, singularity -- is that camera's code, never an error. */
+int  dbat_hip_poseadjust(int32_t device, int32_t n_images, const int64_t *pt_start, const double *X, const double *xn,
+                         const uint8_t *use, const double *w, const dbat_hip_pair_options *opt, double *P, uint8_t *used,
+                         double *dstat, int32_t *istat, double *Q, double *res);
+
 /* ---- measurement hooks -------------------------------------------------- */
 
 /* One benchmark step = one Levenberg-Marquardt iteration's device work at
