@@ -923,20 +923,59 @@ def plan_point_owner(s, shard_count):
     return owner
 
 
+# ---- the calls that take a device index instead of a handle (csrc/batch_host.hpp): what their wrappers share ----
+
+def _ptr(a, t):
+    return None if a is None else a.ctypes.data_as(t)
+
+
+def _out(n, per=1, dtype=float):
+    """Zeros for per values of each of n items -- of one item when n is 0: an output is never a null pointer."""
+    return np.zeros(per * max(n, 1), dtype)
+
+
+def _poses_in(P, n):
+    """(n, 3, 4) poses as 12 column-major doubles each: a copy, padded like an output."""
+    Pf = np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(-1).copy()
+    return np.concatenate([Pf, np.zeros(12)]) if n == 0 else Pf
+
+
+def _poses_out(Pf, n):
+    return Pf[:12 * n].reshape(n, 4, 3).transpose(0, 2, 1)
+
+
+def _mask(use, total):
+    return None if use is None else np.ascontiguousarray(np.broadcast_to(np.asarray(use, bool), (total,))).view(np.uint8)
+
+
+def _weights(w, total):
+    return None if w is None else _f64(np.broadcast_to(np.asarray(w, float), (2, total)))
+
+
+def _adjust_stats(n, ds, ist, Q):
+    """The per-item results dbat_hip_pairadjust and dbat_hip_poseadjust share, from their dstat, istat and Q."""
+    ds, ist = ds[:4 * n].reshape(n, 4), ist[:4 * n].reshape(n, 4)
+    return dict(f0=ds[:, 0].copy(), f=ds[:, 1].copy(), sigma0=ds[:, 2].copy(), lam=ds[:, 3].copy(), code=ist[:, 0].copy(),
+                iters=ist[:, 1].copy(), trials=ist[:, 2].copy(), n_used=ist[:, 3].copy(), Q=Q[:36 * n].reshape(n, 6, 6).transpose(0, 2, 1))
+
+
+def _kernel_ms(family, slots):
+    ms = np.zeros(len(slots))
+    check(getattr(load(), 'dbat_hip_debug_%s_ms' % family)(dptr(ms)))
+    return dict(zip(slots, map(float, ms)))
+
+
 def resect_poses(pt_start, X, xn, tri_start, tri, device=0):
     """dbat_hip_resect: best 3 x 4 camera matrix (n, 3, 4) and rms (n) per camera from its candidate triangles."""
     lib = load()
     n = len(pt_start) - 1
-    ps = np.ascontiguousarray(pt_start, np.int64)
-    ts = np.ascontiguousarray(tri_start, np.int64)
+    ps, ts = np.ascontiguousarray(pt_start, np.int64), np.ascontiguousarray(tri_start, np.int64)
     Xf = np.ascontiguousarray(np.asarray(X, float).flatten('F'))
     xf = np.ascontiguousarray(np.asarray(xn, float).flatten('F'))
     tf = np.ascontiguousarray(np.asarray(tri, np.int32).reshape(-1))
     P, rms = np.empty(12 * n), np.empty(n)
-    i64p = C.POINTER(C.c_int64)
-    check(lib.dbat_hip_resect(int(device), n, ps.ctypes.data_as(i64p), dptr(Xf), dptr(xf), ts.ctypes.data_as(i64p),
-                              tf.ctypes.data_as(_ip), dptr(P), dptr(rms)))
-    return P.reshape(n, 4, 3).transpose(0, 2, 1), rms
+    check(lib.dbat_hip_resect(int(device), n, _ptr(ps, _lp), dptr(Xf), dptr(xf), _ptr(ts, _lp), _ptr(tf, _ip), dptr(P), dptr(rms)))
+    return _poses_out(P, n), rms
 
 
 def essmat5_sets(set_start, Q1, Q2, device=0):
@@ -949,9 +988,8 @@ def essmat5_sets(set_start, Q1, Q2, device=0):
     if Q1.ndim != 2 or Q1.shape[0] != 3 or Q1.shape != Q2.shape or n < 0 or (n >= 0 and Q1.shape[1] != ss[-1]):
         raise ValueError('essmat5: Q1 and Q2 must both be 3-by-n, n the end of the last set')
     q1, q2 = _f64(Q1), _f64(Q2)
-    E, ns = np.zeros(90 * max(n, 1)), np.zeros(max(n, 1), np.int32)
-    check(lib.dbat_hip_essmat5(int(device), n, ss.ctypes.data_as(C.POINTER(C.c_int64)), dptr(q1), dptr(q2), dptr(E),
-                               ns.ctypes.data_as(_ip)))
+    E, ns = _out(n, 90), _out(n, 1, np.int32)
+    check(lib.dbat_hip_essmat5(int(device), n, _ptr(ss, _lp), dptr(q1), dptr(q2), dptr(E), _ptr(ns, _ip)))
     return E[:90 * n].reshape(n, 10, 9), ns[:n]
 
 
@@ -970,13 +1008,11 @@ def relorient_pairs(pt_start, x1, x2, hyp_start, samples, thr2, front_dir, devic
         raise ValueError('relorient: x1 and x2 must both be 2-by-n and samples k-by-5, n and k the ends of the last ranges')
     total = x1.shape[1]
     a, b = _f64(x1), _f64(x2)
-    E, P2, st = np.zeros(9 * max(n, 1)), np.zeros(12 * max(n, 1)), np.zeros(8 * max(n, 1), np.int32)
-    inl, fr, X = np.zeros(max(total, 1), np.uint8), np.zeros(max(total, 1), np.uint8), np.zeros(3 * max(total, 1))
-    i64p = C.POINTER(C.c_int64)
-    check(lib.dbat_hip_relorient(int(device), n, ps.ctypes.data_as(i64p), dptr(a), dptr(b), hs.ctypes.data_as(i64p),
-                                 smp.ctypes.data_as(_ip), dptr(t2), int(front_dir), dptr(E), dptr(P2), st.ctypes.data_as(_ip),
-                                 inl.ctypes.data_as(_bp), fr.ctypes.data_as(_bp), dptr(X)))
-    return dict(E=E[:9 * n].reshape(n, 9), P2=P2[:12 * n].reshape(n, 4, 3).transpose(0, 2, 1), stats=st[:8 * n].reshape(n, 8),
+    E, P2, st = _out(n, 9), _out(n, 12), _out(n, 8, np.int32)
+    inl, fr, X = _out(total, 1, np.uint8), _out(total, 1, np.uint8), _out(total, 3)
+    check(lib.dbat_hip_relorient(int(device), n, _ptr(ps, _lp), dptr(a), dptr(b), _ptr(hs, _lp), _ptr(smp, _ip), dptr(t2),
+                                 int(front_dir), dptr(E), dptr(P2), _ptr(st, _ip), _ptr(inl, _bp), _ptr(fr, _bp), dptr(X)))
+    return dict(E=E[:9 * n].reshape(n, 9), P2=_poses_out(P2, n), stats=st[:8 * n].reshape(n, 8),
                 inlier=inl[:total].astype(bool), in_front=fr[:total].astype(bool), X=X[:3 * total].reshape(3, total, order='F'))
 
 
@@ -990,11 +1026,10 @@ def cams_from_e(e, x1, x2, front_dir, device=0):
     n = x1.shape[1]
     ps = np.array([0, n], np.int64)
     a, b, E, t2 = _f64(x1), _f64(x2), np.ascontiguousarray(np.asarray(e, float).reshape(9)).copy(), np.ones(1)
-    P2, st = np.zeros(12), np.zeros(8, np.int32)
-    inl, fr, X = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8), np.zeros(3 * max(n, 1))
-    check(lib.dbat_hip_relorient(int(device), 1, ps.ctypes.data_as(C.POINTER(C.c_int64)), dptr(a), dptr(b), None, None, dptr(t2),
-                                 int(front_dir), dptr(E), dptr(P2), st.ctypes.data_as(_ip), inl.ctypes.data_as(_bp),
-                                 fr.ctypes.data_as(_bp), dptr(X)))
+    P2, st = _out(1, 12), _out(1, 8, np.int32)
+    inl, fr, X = _out(n, 1, np.uint8), _out(n, 1, np.uint8), _out(n, 3)
+    check(lib.dbat_hip_relorient(int(device), 1, _ptr(ps, _lp), dptr(a), dptr(b), None, None, dptr(t2), int(front_dir), dptr(E),
+                                 dptr(P2), _ptr(st, _ip), _ptr(inl, _bp), _ptr(fr, _bp), dptr(X)))
     return dict(P2=P2.reshape(4, 3).T.copy(), X=X[:3 * n].reshape(3, n, order='F'), in_front=fr[:n].astype(bool), sp=st[4:8].copy())
 
 
@@ -1006,9 +1041,7 @@ def relorient_timing(on=True):
 def relorient_ms():
     """Device-event milliseconds of the kernels of the last essmat5_sets / relorient_pairs call on this thread, after
     relorient_timing(True) (debug)."""
-    ms = np.zeros(3)
-    check(load().dbat_hip_debug_relorient_ms(dptr(ms)))
-    return dict(solve=float(ms[0]), score=float(ms[1]), cams=float(ms[2]))
+    return _kernel_ms('relorient', ('solve', 'score', 'cams'))
 
 
 PAIR_CODES = ('converged', 'max_iter', 'no_step', 'singular', 'too_few')
@@ -1030,24 +1063,16 @@ def pairadjust(pt_start, x1, x2, P2, X, use=None, w1=None, w2=None, front_dir=-1
             or P2.shape[0] != n:
         raise ValueError('pairadjust: x1 and x2 must be 2-by-total, X 3-by-total, total the end of the last range, and P2 one 3-by-4 per pair')
     total = x1.shape[1]
-    a, b = _f64(x1), _f64(x2)
-    wt = [None if w is None else _f64(np.broadcast_to(np.asarray(w, float), (2, total))) for w in (w1, w2)]
-    u = None if use is None else np.ascontiguousarray(np.broadcast_to(np.asarray(use, bool), (total,))).view(np.uint8)
-    P = np.ascontiguousarray(P2.transpose(0, 2, 1)).reshape(-1).copy()
-    P = np.concatenate([P, np.zeros(12)]) if n == 0 else P
-    Xf = X.flatten('F')
-    Xf = np.zeros(3) if total == 0 else Xf
-    used, ds, ist, Q = np.zeros(max(total, 1), np.uint8), np.zeros(4 * max(n, 1)), np.zeros(4 * max(n, 1), np.int32), np.zeros(36 * max(n, 1))
-    res = np.zeros(4 * max(total, 1)) if residuals else None
+    a, b, wa, wb, u = _f64(x1), _f64(x2), _weights(w1, total), _weights(w2, total), _mask(use, total)
+    P = _poses_in(P2, n)
+    Xf = np.zeros(3) if total == 0 else X.flatten('F')
+    used, ds, ist, Q = _out(total, 1, np.uint8), _out(n, 4), _out(n, 4, np.int32), _out(n, 36)
+    res = _out(total, 4) if residuals else None
     opt = PairOptions(int(max_iter), float(conv_tol), float(min_angle))
-    check(lib.dbat_hip_pairadjust(int(device), n, ps.ctypes.data_as(C.POINTER(C.c_int64)), dptr(a), dptr(b),
-                                  None if u is None else u.ctypes.data_as(_bp), dptr(wt[0]), dptr(wt[1]), int(front_dir), C.byref(opt),
-                                  dptr(P), dptr(Xf), used.ctypes.data_as(_bp), dptr(ds), ist.ctypes.data_as(_ip), dptr(Q), dptr(res)))
-    ds, ist = ds[:4 * n].reshape(n, 4), ist[:4 * n].reshape(n, 4)
-    return dict(P2=P[:12 * n].reshape(n, 4, 3).transpose(0, 2, 1), X=Xf[:3 * total].reshape(3, total, order='F'), used=used[:total].astype(bool),
-                f0=ds[:, 0].copy(), f=ds[:, 1].copy(), sigma0=ds[:, 2].copy(), lam=ds[:, 3].copy(), code=ist[:, 0].copy(),
-                iters=ist[:, 1].copy(), trials=ist[:, 2].copy(), n_used=ist[:, 3].copy(), Q=Q[:36 * n].reshape(n, 6, 6).transpose(0, 2, 1),
-                res=None if res is None else res[:4 * total].reshape(total, 2, 2).transpose(1, 2, 0))
+    check(lib.dbat_hip_pairadjust(int(device), n, _ptr(ps, _lp), dptr(a), dptr(b), _ptr(u, _bp), dptr(wa), dptr(wb), int(front_dir),
+                                  C.byref(opt), dptr(P), dptr(Xf), _ptr(used, _bp), dptr(ds), _ptr(ist, _ip), dptr(Q), dptr(res)))
+    return dict(P2=_poses_out(P, n), X=Xf[:3 * total].reshape(3, total, order='F'), used=used[:total].astype(bool),
+                **_adjust_stats(n, ds, ist, Q), res=None if res is None else res[:4 * total].reshape(total, 2, 2).transpose(1, 2, 0))
 
 
 def pairadjust_timing(on=True):
@@ -1058,9 +1083,7 @@ def pairadjust_timing(on=True):
 def pairadjust_ms():
     """Device-event milliseconds of the kernel of the last pairadjust call on this thread, after pairadjust_timing(True)
     (debug)."""
-    ms = np.zeros(1)
-    check(load().dbat_hip_debug_pairadjust_ms(dptr(ms)))
-    return float(ms[0])
+    return _kernel_ms('pairadjust', ('kernel',))['kernel']
 
 
 def resect_ransac(pt_start, X, xn, smp_start, samples, thr2, use=None, device=0):
@@ -1077,15 +1100,11 @@ def resect_ransac(pt_start, X, xn, smp_start, samples, thr2, use=None, device=0)
     if n < 0 or len(ss) != n + 1 or X.ndim != 2 or X.shape[0] != 3 or xn.shape != (2, X.shape[1]) or X.shape[1] != ps[-1] or smp.shape[0] != ss[-1]:
         raise ValueError('resect_ransac: X must be 3-by-total, xn 2-by-total and samples k-by-3, total and k the ends of the last ranges')
     total = X.shape[1]
-    Xf, xf = _f64(X), _f64(xn)
-    u = None if use is None else np.ascontiguousarray(np.broadcast_to(np.asarray(use, bool), (total,))).view(np.uint8)
-    P, st, ssq = np.zeros(12 * max(n, 1)), np.zeros(4 * max(n, 1), np.int32), np.zeros(max(n, 1))
-    inl = np.zeros(max(total, 1), np.uint8)
-    i64p = C.POINTER(C.c_int64)
-    check(lib.dbat_hip_resect_ransac(int(device), n, ps.ctypes.data_as(i64p), dptr(Xf), dptr(xf), None if u is None else u.ctypes.data_as(_bp),
-                                     ss.ctypes.data_as(i64p), smp.ctypes.data_as(_ip), dptr(t2), dptr(P), st.ctypes.data_as(_ip),
-                                     inl.ctypes.data_as(_bp), dptr(ssq)))
-    return dict(P=P[:12 * n].reshape(n, 4, 3).transpose(0, 2, 1), stats=st[:4 * n].reshape(n, 4), inlier=inl[:total].astype(bool), ssq=ssq[:n])
+    Xf, xf, u = _f64(X), _f64(xn), _mask(use, total)
+    P, st, ssq, inl = _out(n, 12), _out(n, 4, np.int32), _out(n), _out(total, 1, np.uint8)
+    check(lib.dbat_hip_resect_ransac(int(device), n, _ptr(ps, _lp), dptr(Xf), dptr(xf), _ptr(u, _bp), _ptr(ss, _lp), _ptr(smp, _ip),
+                                     dptr(t2), dptr(P), _ptr(st, _ip), _ptr(inl, _bp), dptr(ssq)))
+    return dict(P=_poses_out(P, n), stats=st[:4 * n].reshape(n, 4), inlier=inl[:total].astype(bool), ssq=ssq[:n])
 
 
 def poseadjust(pt_start, X, xn, P, use=None, w=None, max_iter=20, conv_tol=1e-6, min_angle=0.0, residuals=False, device=0):
@@ -1102,21 +1121,14 @@ def poseadjust(pt_start, X, xn, P, use=None, w=None, max_iter=20, conv_tol=1e-6,
     if n < 0 or X.ndim != 2 or X.shape[0] != 3 or xn.shape != (2, X.shape[1]) or X.shape[1] != ps[-1] or P.shape[0] != n:
         raise ValueError('poseadjust: X must be 3-by-total, xn 2-by-total, total the end of the last range, and P one 3-by-4 per camera')
     total = X.shape[1]
-    Xf, xf = _f64(X), _f64(xn)
-    wt = None if w is None else _f64(np.broadcast_to(np.asarray(w, float), (2, total)))
-    u = None if use is None else np.ascontiguousarray(np.broadcast_to(np.asarray(use, bool), (total,))).view(np.uint8)
-    Pf = np.ascontiguousarray(P.transpose(0, 2, 1)).reshape(-1).copy()
-    Pf = np.concatenate([Pf, np.zeros(12)]) if n == 0 else Pf
-    used, ds, ist, Q = np.zeros(max(total, 1), np.uint8), np.zeros(4 * max(n, 1)), np.zeros(4 * max(n, 1), np.int32), np.zeros(36 * max(n, 1))
-    res = np.zeros(2 * max(total, 1)) if residuals else None
+    Xf, xf, wt, u = _f64(X), _f64(xn), _weights(w, total), _mask(use, total)
+    Pf = _poses_in(P, n)
+    used, ds, ist, Q = _out(total, 1, np.uint8), _out(n, 4), _out(n, 4, np.int32), _out(n, 36)
+    res = _out(total, 2) if residuals else None
     opt = PairOptions(int(max_iter), float(conv_tol), float(min_angle))
-    check(lib.dbat_hip_poseadjust(int(device), n, ps.ctypes.data_as(C.POINTER(C.c_int64)), dptr(Xf), dptr(xf),
-                                  None if u is None else u.ctypes.data_as(_bp), dptr(wt), C.byref(opt), dptr(Pf),
-                                  used.ctypes.data_as(_bp), dptr(ds), ist.ctypes.data_as(_ip), dptr(Q), dptr(res)))
-    ds, ist = ds[:4 * n].reshape(n, 4), ist[:4 * n].reshape(n, 4)
-    return dict(P=Pf[:12 * n].reshape(n, 4, 3).transpose(0, 2, 1), used=used[:total].astype(bool), f0=ds[:, 0].copy(), f=ds[:, 1].copy(),
-                sigma0=ds[:, 2].copy(), lam=ds[:, 3].copy(), code=ist[:, 0].copy(), iters=ist[:, 1].copy(), trials=ist[:, 2].copy(),
-                n_used=ist[:, 3].copy(), Q=Q[:36 * n].reshape(n, 6, 6).transpose(0, 2, 1),
+    check(lib.dbat_hip_poseadjust(int(device), n, _ptr(ps, _lp), dptr(Xf), dptr(xf), _ptr(u, _bp), dptr(wt), C.byref(opt), dptr(Pf),
+                                  _ptr(used, _bp), dptr(ds), _ptr(ist, _ip), dptr(Q), dptr(res)))
+    return dict(P=_poses_out(Pf, n), used=used[:total].astype(bool), **_adjust_stats(n, ds, ist, Q),
                 res=None if res is None else res[:2 * total].reshape(total, 2).T)
 
 
@@ -1128,9 +1140,7 @@ def resect_robust_timing(on=True):
 def resect_robust_ms():
     """Device-event milliseconds of the kernels of the last resect_ransac and poseadjust calls on this thread, after
     resect_robust_timing(True) (debug)."""
-    ms = np.zeros(2)
-    check(load().dbat_hip_debug_resect_robust_ms(dptr(ms)))
-    return dict(ransac=float(ms[0]), adjust=float(ms[1]))
+    return _kernel_ms('resect_robust', ('ransac', 'adjust'))
 
 
 def rigidalign(X, Y, scale=False, use=None, resid=False, device=0):
@@ -1149,8 +1159,7 @@ def rigidalign(X, Y, scale=False, use=None, resid=False, device=0):
             raise ValueError('rigidalign: use must have one entry per column')
     T, st = np.zeros(16), np.zeros(4)
     r = np.empty(3 * n) if resid else None
-    check(lib.dbat_hip_rigidalign(int(device), n, dptr(Xf), dptr(Yf), None if u is None else u.ctypes.data_as(_bp),
-                                  int(bool(scale)), dptr(T), dptr(st), dptr(r)))
+    check(lib.dbat_hip_rigidalign(int(device), n, dptr(Xf), dptr(Yf), _ptr(u, _bp), int(bool(scale)), dptr(T), dptr(st), dptr(r)))
     return (T.reshape(4, 4, order='F'), dict(alpha=float(st[0]), rms=float(st[1]), used=int(st[2]), sv_ratio=float(st[3])),
             None if r is None else r.reshape(3, n, order='F'))
 
@@ -1169,9 +1178,9 @@ def multixform(EO, OP, T, device=0):
     nc, npnt = (EO.shape[1] if EO.size else 0), (OP.shape[1] if OP.size else 0)
     rows = EO.shape[0] if nc else 6
     eo, op = np.array(EO, float, order='F'), np.array(OP, float, order='F')
-    fail = np.zeros(max(nc, 1), np.uint8)
+    fail = _out(nc, 1, np.uint8)
     check(lib.dbat_hip_multixform(int(device), dptr(_f64(T)), nc, int(rows), dptr(eo.reshape(-1, order='F')) if nc else None,
-                                  npnt, dptr(op.reshape(-1, order='F')) if npnt else None, fail.ctypes.data_as(_bp)))
+                                  npnt, dptr(op.reshape(-1, order='F')) if npnt else None, _ptr(fail, _bp)))
     return eo, op, fail[:nc].astype(bool)
 
 
@@ -1183,9 +1192,7 @@ def align_timing(on=True):
 def align_ms():
     """Device-event milliseconds of the kernels of the last rigidalign / multixform call on this thread, after
     align_timing(True) (debug)."""
-    ms = np.zeros(5)
-    check(load().dbat_hip_debug_align_ms(dptr(ms)))
-    return dict(centroid=float(ms[0]), cross=float(ms[1]), resid=float(ms[2]), points=float(ms[3]), cams=float(ms[4]))
+    return _kernel_ms('align', ('centroid', 'cross', 'resid', 'points', 'cams'))
 
 
 def plan_layout_stats(s, shard_rank=0, shard_count=1):

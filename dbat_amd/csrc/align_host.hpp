@@ -3,10 +3,9 @@
 #pragma once
 
 namespace dbat {
-// device events around the kernels of the last call on this thread: [0] centroids [1] cross products [2] residuals
-// (dbat_hip_rigidalign), [3] points [4] cameras (dbat_hip_multixform), each pass with its finishing launch; 0: not launched
-static thread_local double g_align_ms[5] = {0, 0, 0, 0, 0};
-static thread_local bool g_align_timing = false;         // dbat_hip_debug_align_timing: off, no event is created
+// the kernels of the last call on this thread: [0] centroids [1] cross products [2] residuals (dbat_hip_rigidalign),
+// [3] points [4] cameras (dbat_hip_multixform), each pass with its finishing launch
+using AlignClock = KernelClock<struct AlignFamily, 5>;
 
 static const char *const ALIGN_COLLINEAR = "rigidalign: the used points are collinear or coincide (second singular value of the "
                                            "cross-product matrix <= 1e-12 of the first): the rotation is not defined";
@@ -38,11 +37,7 @@ int dbat_hip_rigidalign(int32_t device, int64_t n, const double *X, const double
         al_svd3(Cxy, U, s, V);
         if (!(s[1] > 1e-12 * s[0])) { g_err = ALIGN_COLLINEAR; return DBAT_HIP_EINVAL; }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device: the dbat_hip core has no CPU path"; return DBAT_HIP_EDEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "bad device index"; return DBAT_HIP_EINVAL; }
-    DeviceGuard dev_guard(device);
-    const hipStream_t st = nullptr;
+    BatchDevice dev(device);                          // (no early return for n == 0: fewer than three columns were refused)
     const int G = (int)al_grid(n);
     DevBuf<double> dX, dY, part, out, dres;
     DevBuf<uint8_t> duse;
@@ -51,16 +46,17 @@ int dbat_hip_rigidalign(int32_t device, int64_t n, const double *X, const double
     part.alloc((size_t)10 * G); out.alloc(18);
     EventTimer<2> e01;
     EventTimer<1> e2;
-    if (g_align_timing) e01.start(st);
-    launch<k_align_centroid>(dim3(G), dim3(AL_WG), 0, st, n, dX.p, dY.p, duse.p, part.p);
-    launch<k_align_finish<7, true>>(dim3(1), dim3(AL_WG), 0, st, G, part.p, out.p);
-    e01.lap(st);
-    launch<k_align_cross>(dim3(G), dim3(AL_WG), 0, st, n, dX.p, dY.p, duse.p, out.p, part.p);
-    launch<k_align_finish<10, false>>(dim3(1), dim3(AL_WG), 0, st, G, part.p, out.p + 7);
-    e01.lap(st);
+    AlignClock::start(e01, dev.st);
+    launch<k_align_centroid>(dim3(G), dim3(AL_WG), 0, dev.st, n, dX.p, dY.p, duse.p, part.p);
+    launch<k_align_finish<7, true>>(dim3(1), dim3(AL_WG), 0, dev.st, G, part.p, out.p);
+    e01.lap(dev.st);
+    launch<k_align_cross>(dim3(G), dim3(AL_WG), 0, dev.st, n, dX.p, dY.p, duse.p, out.p, part.p);
+    launch<k_align_finish<10, false>>(dim3(1), dim3(AL_WG), 0, dev.st, G, part.p, out.p + 7);
+    e01.lap(dev.st);
     double h[18];
     HIPCHK(hipMemcpy(h, out.p, 17 * sizeof(double), hipMemcpyDeviceToHost));
-    g_align_ms[0] = e01.read(); g_align_ms[1] = e01.ms[1]; g_align_ms[2] = g_align_ms[3] = g_align_ms[4] = 0;
+    double *const ms = AlignClock::ms;
+    ms[0] = e01.read(); ms[1] = e01.ms[1]; ms[2] = ms[3] = ms[4] = 0;
     // rigidalign.m:46-61
     AlignPar ap;
     double R[9], s[3];
@@ -77,13 +73,13 @@ int dbat_hip_rigidalign(int32_t device, int64_t n, const double *X, const double
     for (int i = 0; i < 9; ++i) { ap.aR[i] = alpha * R[i]; ap.aRl[i] = std::fma(alpha, R[i], -ap.aR[i]); }
     for (int k = 0; k < 3; ++k) d[k] = ap.ym[k] - (ap.aR[k] * ap.xm[0] + ap.aR[3 + k] * ap.xm[1] + ap.aR[6 + k] * ap.xm[2]);
     if (resid) dres.alloc((size_t)3 * n);
-    if (g_align_timing) e2.start(st);
-    launch<k_align_resid>(dim3(G), dim3(AL_WG), 0, st, n, dX.p, dY.p, duse.p, ap, dres.p, part.p);
-    launch<k_align_finish<1, false>>(dim3(1), dim3(AL_WG), 0, st, G, part.p, out.p + 17);
-    e2.lap(st);
+    AlignClock::start(e2, dev.st);
+    launch<k_align_resid>(dim3(G), dim3(AL_WG), 0, dev.st, n, dX.p, dY.p, duse.p, ap, dres.p, part.p);
+    launch<k_align_finish<1, false>>(dim3(1), dim3(AL_WG), 0, dev.st, G, part.p, out.p + 17);
+    e2.lap(dev.st);
     HIPCHK(hipMemcpy(h + 17, out.p + 17, sizeof(double), hipMemcpyDeviceToHost));
-    if (resid) HIPCHK(hipMemcpy(resid, dres.p, (size_t)3 * n * sizeof(double), hipMemcpyDeviceToHost));
-    g_align_ms[2] = e2.read();
+    dres.download(resid);                            // (empty without resid)
+    ms[2] = e2.read();
     for (int j = 0; j < 3; ++j) {
         for (int i = 0; i < 3; ++i) T[4 * j + i] = ap.aR[3 * j + i];
         T[4 * j + 3] = 0; T[12 + j] = d[j];
@@ -101,21 +97,17 @@ int dbat_hip_multixform(int32_t device, const double *T, int64_t n_images, int32
     XformPar par;
     double alpha = 1.0;
     if (const char *e = al_similarity(T, par, alpha)) { g_err = std::string("multixform: ") + e; return DBAT_HIP_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device: the dbat_hip core has no CPU path"; return DBAT_HIP_EDEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "bad device index"; return DBAT_HIP_EINVAL; }
-    DeviceGuard dev_guard(device);
-    const hipStream_t st = nullptr;
-    for (int i = 0; i < 5; ++i) g_align_ms[i] = 0;
+    BatchDevice dev(device);
+    std::fill(AlignClock::ms, AlignClock::ms + 5, 0.0);
     if (n_points > 0) {
         DevBuf<double> dOP;
         dOP.upload(OP, (size_t)3 * n_points);
         EventTimer<1> ev;
-        if (g_align_timing) ev.start(st);
-        launch<k_xform_points>(dim3((unsigned)cdiv(n_points, AL_WG)), dim3(AL_WG), 0, st, n_points, dOP.p, par);
-        ev.lap(st);
-        HIPCHK(hipMemcpy(OP, dOP.p, (size_t)3 * n_points * sizeof(double), hipMemcpyDeviceToHost));
-        g_align_ms[3] = ev.read();
+        AlignClock::start(ev, dev.st);
+        launch<k_xform_points>(dim3((unsigned)cdiv(n_points, AL_WG)), dim3(AL_WG), 0, dev.st, n_points, dOP.p, par);
+        ev.lap(dev.st);
+        dOP.download(OP);
+        AlignClock::ms[3] = ev.read();
     }
     if (n_images > 0) {
         DevBuf<double> dEO;
@@ -123,12 +115,12 @@ int dbat_hip_multixform(int32_t device, const double *T, int64_t n_images, int32
         dEO.upload(EO, (size_t)eo_rows * n_images);
         dfail.alloc((size_t)n_images);
         EventTimer<1> ev;
-        if (g_align_timing) ev.start(st);
-        launch<k_xform_cams>(dim3((unsigned)cdiv(n_images, AL_WG)), dim3(AL_WG), 0, st, n_images, (int)eo_rows, dEO.p, par, dfail.p);
-        ev.lap(st);
-        HIPCHK(hipMemcpy(EO, dEO.p, (size_t)eo_rows * n_images * sizeof(double), hipMemcpyDeviceToHost));
-        if (fail) HIPCHK(hipMemcpy(fail, dfail.p, (size_t)n_images, hipMemcpyDeviceToHost));
-        g_align_ms[4] = ev.read();
+        AlignClock::start(ev, dev.st);
+        launch<k_xform_cams>(dim3((unsigned)cdiv(n_images, AL_WG)), dim3(AL_WG), 0, dev.st, n_images, (int)eo_rows, dEO.p, par, dfail.p);
+        ev.lap(dev.st);
+        dEO.download(EO);
+        if (fail) dfail.download(fail);
+        AlignClock::ms[4] = ev.read();
     }
     return DBAT_HIP_OK;
     API_CATCH
@@ -138,10 +130,6 @@ int dbat_hip_multixform(int32_t device, const double *T, int64_t n_images, int32
  * bracket their kernels with device events (off by default: a product call creates none); dbat_hip_debug_align_ms then
  * gives the milliseconds of the last call: ms[0] centroids, ms[1] cross products, ms[2] residuals, ms[3] points, ms[4]
  * cameras; each pass with its finishing launch; 0 for what the last call did not launch or did not time. */
-int dbat_hip_debug_align_timing(int32_t on) { g_align_timing = on != 0; return DBAT_HIP_OK; }
-int dbat_hip_debug_align_ms(double *ms) {
-    if (!ms) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    for (int i = 0; i < 5; ++i) ms[i] = g_align_ms[i];
-    return DBAT_HIP_OK;
-}
+int dbat_hip_debug_align_timing(int32_t on) { return AlignClock::set(on); }
+int dbat_hip_debug_align_ms(double *ms) { return AlignClock::get(ms); }
 }  // extern "C"

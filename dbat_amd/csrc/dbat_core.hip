@@ -103,6 +103,7 @@ struct DevBuf {
     }
     template <class A>
     void upload(const std::vector<T, A> &v) { upload(v.data(), v.size()); }
+    void download(T *dst) const { if (n) HIPCHK(hipMemcpy(dst, p, n * sizeof(T), hipMemcpyDeviceToHost)); }   // synchronous, all of it
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
 
@@ -954,6 +955,10 @@ struct Core {
     void build_tail_enqueue(const double *zz, int64_t npart) {
         launch<k_build_tail>(dim3(grid_zs), dim3(1024), 0, d, zz, partial.p, npart, jn2p.p, gpart.p, gctr.p + CTR_BUILD_TAIL, red_scal,
                 zz != zlin.p ? zlin.p : (double *)nullptr);
+        // deterministic mode on the signature route: a wave of k_build_sig sums r'r over whichever chunks it took, so that
+        // sum's last bit moves from run to run; the camera side, which this mode runs over EVERY observation, has the same
+        // sum (with the prior rows' squares) in a fixed order (k_det_rows).  (The other kernels' blocks have fixed work.)
+        if (deterministic && route == TileRoute::sig) HIPCHK(hipMemcpyAsync(red_scal, det_rr.p + P.nc, sizeof(double), hipMemcpyDeviceToDevice, stream));
     }
     // measurement build (ablation bit 32): the phase clocks g_tile2_prof[first, first + count), averaged over n workgroups; clears from first on
     void dump_phase_profile(const char *title, const char *unit, const char *const *names, int first, int count, int64_t n) {
@@ -1613,6 +1618,7 @@ static const char *solve_args_error(const dbat_hip_handle *h, const dbat_hip_opt
 #include "quality_host.hpp"
 #include "cov_host.hpp"
 #include "export_host.hpp"
+#include "batch_host.hpp"         // what the calls without a handle share: dbat_hip_resect below, the others at the end
 #include "initial_host.hpp"
 #include "debug_host.hpp"
 

@@ -41,9 +41,8 @@ int dbat_hip_resect(int32_t device, int32_t n_images, const int64_t *pt_start, c
                     const int64_t *tri_start, const int32_t *tri, double *P, double *rms) {
     API_TRY
     if (n_images < 0 || !pt_start || !tri_start || !P || !rms) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device: the dbat_hip core has no CPU path"; return DBAT_HIP_EDEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "bad device index"; return DBAT_HIP_EINVAL; }
+    // (the oldest of the family: the device before the ranges, no prefix in the messages, a triangle may repeat an index)
+    BatchDevice dev(device);
     if (n_images == 0) return DBAT_HIP_OK;
     if (pt_start[0] != 0 || tri_start[0] != 0) { g_err = "ranges must start at 0"; return DBAT_HIP_EINVAL; }
     for (int c = 0; c < n_images; ++c)
@@ -53,16 +52,14 @@ int dbat_hip_resect(int32_t device, int32_t n_images, const int64_t *pt_start, c
     for (int c = 0; c < n_images; ++c)
         for (int64_t t = 3 * tri_start[c]; t < 3 * tri_start[c + 1]; ++t)
             if (tri[t] < 0 || tri[t] >= pt_start[c + 1] - pt_start[c]) { g_err = "triangle index outside the camera's points"; return DBAT_HIP_EINVAL; }
-    DeviceGuard dev_guard(device);
     DevBuf<int64_t> dps, dts;
     DevBuf<double> dX, dx, dP, dr;
     DevBuf<int32_t> dtri;
     dps.upload(pt_start, (size_t)n_images + 1); dts.upload(tri_start, (size_t)n_images + 1);
     dX.upload(X, (size_t)3 * npt); dx.upload(xn, (size_t)2 * npt); dtri.upload(tri, (size_t)3 * ntri);
     dP.alloc((size_t)12 * n_images); dr.alloc((size_t)n_images);
-    launch<k_resect>(dim3((unsigned)n_images), dim3(64), 0, (hipStream_t)nullptr, n_images, dps.p, dX.p, dx.p, dts.p, dtri.p, 1, dP.p, dr.p);
-    HIPCHK(hipMemcpy(P, dP.p, (size_t)12 * n_images * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(rms, dr.p, (size_t)n_images * sizeof(double), hipMemcpyDeviceToHost));
+    launch<k_resect>(dim3((unsigned)n_images), dim3(64), 0, dev.st, n_images, dps.p, dX.p, dx.p, dts.p, dtri.p, 1, dP.p, dr.p);
+    dP.download(P); dr.download(rms);
     return DBAT_HIP_OK;
     API_CATCH
 }

@@ -3,9 +3,7 @@
 #pragma once
 
 namespace dbat {
-// device events around k_pairadjust of the last call on this thread; 0: not launched
-static thread_local double g_pairadjust_ms = 0;
-static thread_local bool g_pairadjust_timing = false;    // dbat_hip_debug_pairadjust_timing: off, no event is created
+using PairadjustClock = KernelClock<struct PairadjustFamily, 1>;    // k_pairadjust of the last call on this thread
 }  // namespace dbat
 
 extern "C" {
@@ -22,40 +20,20 @@ int dbat_hip_pairadjust(int32_t device, int32_t n_pairs, const int64_t *pt_start
     API_TRY
     if (n_pairs < 0 || !pt_start || !opt || !P2 || !dstat || !istat || !Q) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
     if (front_dir != 1 && front_dir != -1) { g_err = "pairadjust: front_dir must be +1 or -1"; return DBAT_HIP_EINVAL; }
-    if (opt->max_iter < 1 || opt->max_iter > 200) { g_err = "pairadjust: max_iter must be 1 .. 200"; return DBAT_HIP_EINVAL; }
-    if (!(opt->conv_tol > 0) || !std::isfinite(opt->conv_tol)) { g_err = "pairadjust: conv_tol must be positive"; return DBAT_HIP_EINVAL; }
+    check_pair_options("pairadjust", opt);
     if (!(opt->min_angle >= 0 && opt->min_angle < 1.5707963267948966)) { g_err = "pairadjust: min_angle must lie in [0, pi/2)"; return DBAT_HIP_EINVAL; }
-    if (pt_start[0] != 0) { g_err = "pairadjust: ranges must start at 0"; return DBAT_HIP_EINVAL; }
-    for (int32_t p = 0; p < n_pairs; ++p)
-        if (pt_start[p + 1] < pt_start[p]) { g_err = "pairadjust: the ranges of pt_start must ascend"; return DBAT_HIP_EINVAL; }
+    check_ranges("pairadjust", "pt_start", n_pairs, pt_start);       // (no cap on the points of a pair, where poseadjust has 2^29)
     const int64_t total = pt_start[n_pairs];
     if (total > 0 && (!x1 || !x2 || !X || !used)) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    for (int64_t i = 0; i < 2 * total; ++i) {
-        if (!std::isfinite(x1[i]) || !std::isfinite(x2[i])) { g_err = "pairadjust: correspondence " + std::to_string(i / 2) + " is not finite"; return DBAT_HIP_EINVAL; }
-        for (const double *w : {w1, w2})
-            if (w && (!std::isfinite(w[i]) || !(w[i] > 0))) { g_err = "pairadjust: weight of correspondence " + std::to_string(i / 2) + " is not positive and finite"; return DBAT_HIP_EINVAL; }
-    }
-    for (int64_t g = 0; g < total; ++g)
-        if ((!use || use[g]) && !(std::isfinite(X[3 * g]) && std::isfinite(X[3 * g + 1]) && std::isfinite(X[3 * g + 2]))) {
-            g_err = "pairadjust: point " + std::to_string(g) + " is to be used and is not finite"; return DBAT_HIP_EINVAL;
-        }
+    check_columns("pairadjust", "correspondence", 2, total, x1, x2, w1, w2);
+    check_used_points("pairadjust", total, use, X);
     for (int32_t p = 0; p < n_pairs; ++p) {
         const double *P = P2 + 12 * (size_t)p;
-        for (int i = 0; i < 12; ++i)
-            if (!std::isfinite(P[i])) { g_err = "pairadjust: P2 of pair " + std::to_string(p) + " is not finite"; return DBAT_HIP_EINVAL; }
-        double dev = 0;
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b)
-                dev = std::max(dev, std::fabs(P[3 * a] * P[3 * b] + P[3 * a + 1] * P[3 * b + 1] + P[3 * a + 2] * P[3 * b + 2] - (a == b ? 1.0 : 0.0)));
-        if (dev > 1e-6 || al_det3(P) < 0) { g_err = "pairadjust: R of pair " + std::to_string(p) + " is not a rotation"; return DBAT_HIP_EINVAL; }
+        check_pose("pairadjust", "P2", "pair", p, P);
         if (P[9] == 0 && P[10] == 0 && P[11] == 0) { g_err = "pairadjust: t of pair " + std::to_string(p) + " is zero"; return DBAT_HIP_EINVAL; }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device: the dbat_hip core has no CPU path"; return DBAT_HIP_EDEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "bad device index"; return DBAT_HIP_EINVAL; }
+    BatchDevice dev(device);
     if (n_pairs == 0) return DBAT_HIP_OK;
-    DeviceGuard dev_guard(device);
-    const hipStream_t st = nullptr;
     // t comes at unit length: the gauge of camsfrome
     std::vector<double> Pn(P2, P2 + 12 * (size_t)n_pairs);
     for (int32_t p = 0; p < n_pairs; ++p) {
@@ -77,28 +55,21 @@ int dbat_hip_pairadjust(int32_t device, int32_t n_pairs, const int64_t *pt_start
     if (use) duse.upload(use, tot1);
     dP.upload(Pn); dX.upload(X, 3 * tot1); dXt.alloc(3 * tot1); dused.alloc(tot1);
     dds.alloc((size_t)4 * n_pairs); dis.alloc((size_t)4 * n_pairs); dQ.alloc((size_t)36 * n_pairs);
-    if (res && total > 0) { dres.alloc(4 * tot1); HIPCHK(hipMemsetAsync(dres.p, 0, 4 * tot1 * sizeof(double), st)); }
+    if (res && total > 0) { dres.alloc(4 * tot1); HIPCHK(hipMemsetAsync(dres.p, 0, 4 * tot1 * sizeof(double), dev.st)); }
     EventTimer<1> ev;
-    if (g_pairadjust_timing) ev.start(st);
-    launch<k_pairadjust>(dim3((unsigned)n_pairs), dim3(PA_WG), 0, st, (const int64_t *)dps.p, (const double *)dx1.p, (const double *)dx2.p,
+    PairadjustClock::start(ev, dev.st);
+    launch<k_pairadjust>(dim3((unsigned)n_pairs), dim3(PA_WG), 0, dev.st, (const int64_t *)dps.p, (const double *)dx1.p, (const double *)dx2.p,
                          (const uint8_t *)(use ? duse.p : nullptr), (const double *)(w1 ? dw1.p : nullptr),
                          (const double *)(w2 ? dw2.p : nullptr), (int)front_dir, (int)opt->max_iter, opt->conv_tol * opt->conv_tol, s * s,
                          dP.p, dX.p, dXt.p, dused.p, dds.p, dis.p, dQ.p, (double *)dres.p);
-    ev.lap(st);
+    ev.lap(dev.st);
     // a pair of fewer than five used correspondences returns P2 as given: the bits of the caller's, not the unit-length copy
     std::vector<double> Pout((size_t)12 * n_pairs);
-    HIPCHK(hipMemcpy(Pout.data(), dP.p, Pout.size() * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(istat, dis.p, (size_t)4 * n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(dstat, dds.p, (size_t)4 * n_pairs * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(Q, dQ.p, (size_t)36 * n_pairs * sizeof(double), hipMemcpyDeviceToHost));
+    dP.download(Pout.data()); dis.download(istat); dds.download(dstat); dQ.download(Q);
     for (int32_t p = 0; p < n_pairs; ++p)
         if (istat[4 * (size_t)p] != PA_TOO_FEW) std::copy(Pout.begin() + 12 * (size_t)p, Pout.begin() + 12 * (size_t)(p + 1), P2 + 12 * (size_t)p);
-    if (total > 0) {
-        HIPCHK(hipMemcpy(X, dX.p, (size_t)3 * total * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(used, dused.p, (size_t)total, hipMemcpyDeviceToHost));
-        if (res) HIPCHK(hipMemcpy(res, dres.p, (size_t)4 * total * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    g_pairadjust_ms = ev.read();
+    dX.download(X); dused.download(used); dres.download(res);     // (empty without points; dres without res)
+    PairadjustClock::ms[0] = ev.read();
     return DBAT_HIP_OK;
     API_CATCH
 }
@@ -106,10 +77,6 @@ int dbat_hip_pairadjust(int32_t device, int32_t n_pairs, const int64_t *pt_start
 /* Debug / measurement: dbat_hip_debug_pairadjust_timing(1) makes dbat_hip_pairadjust on this thread bracket its kernel with
  * device events (off by default: a product call creates none); dbat_hip_debug_pairadjust_ms then gives the milliseconds
  * of the last call's k_pairadjust. */
-int dbat_hip_debug_pairadjust_timing(int32_t on) { g_pairadjust_timing = on != 0; return DBAT_HIP_OK; }
-int dbat_hip_debug_pairadjust_ms(double *ms) {
-    if (!ms) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    ms[0] = g_pairadjust_ms;
-    return DBAT_HIP_OK;
-}
+int dbat_hip_debug_pairadjust_timing(int32_t on) { return PairadjustClock::set(on); }
+int dbat_hip_debug_pairadjust_ms(double *ms) { return PairadjustClock::get(ms); }
 }  // extern "C"

@@ -3,10 +3,8 @@
 #pragma once
 
 namespace dbat {
-// device events around the kernels of the last call on this thread: [0] k_essmat5 [1] k_ro_score with k_ro_winner
-// [2] the two passes of k_ro_cams; 0: not launched
-static thread_local double g_relorient_ms[3] = {0, 0, 0};
-static thread_local bool g_relorient_timing = false;     // dbat_hip_debug_relorient_timing: off, no event is created
+// the kernels of the last call on this thread: [0] k_essmat5 [1] k_ro_score with k_ro_winner [2] the two passes of k_ro_cams
+using RelorientClock = KernelClock<struct RelorientFamily, 3>;
 
 static void ro_launch_essmat5(hipStream_t st, int64_t n_sets, const int64_t *set_start, const double *Q1, const double *Q2,
                               const int64_t *idx, double *E, int32_t *n_sol) {
@@ -43,32 +41,26 @@ extern "C" {
 int dbat_hip_essmat5(int32_t device, int32_t n_sets, const int64_t *set_start, const double *Q1, const double *Q2, double *E, int32_t *n_sol) {
     API_TRY
     if (n_sets < 0 || !set_start || !E || !n_sol) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    if (set_start[0] != 0) { g_err = "essmat5: ranges must start at 0"; return DBAT_HIP_EINVAL; }
+    check_ranges_start("essmat5", set_start);
     for (int32_t s = 0; s < n_sets; ++s)
-        if (set_start[s + 1] - set_start[s] < 5) { g_err = "essmat5: set " + std::to_string(s) + " has fewer than five correspondences"; return DBAT_HIP_EINVAL; }
+        if (set_start[s + 1] - set_start[s] < 5) refuse("essmat5", "set " + std::to_string(s) + " has fewer than five correspondences");
     const int64_t total = set_start[n_sets];
     if (total > 0 && (!Q1 || !Q2)) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    for (int64_t i = 0; i < 3 * total; ++i)
-        if (!std::isfinite(Q1[i]) || !std::isfinite(Q2[i])) { g_err = "essmat5: correspondence " + std::to_string(i / 3) + " is not finite"; return DBAT_HIP_EINVAL; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device: the dbat_hip core has no CPU path"; return DBAT_HIP_EDEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "bad device index"; return DBAT_HIP_EINVAL; }
+    check_columns("essmat5", "correspondence", 3, total, Q1, Q2);
+    BatchDevice dev(device);
     if (n_sets == 0) return DBAT_HIP_OK;
-    DeviceGuard dev_guard(device);
-    const hipStream_t st = nullptr;
     DevBuf<int64_t> dss;
     DevBuf<double> dQ1, dQ2, dE;
     DevBuf<int32_t> dn;
     dss.upload(set_start, (size_t)n_sets + 1); dQ1.upload(Q1, (size_t)3 * total); dQ2.upload(Q2, (size_t)3 * total);
     dE.alloc((size_t)90 * n_sets); dn.alloc((size_t)n_sets);
-    HIPCHK(hipMemsetAsync(dE.p, 0, (size_t)90 * n_sets * sizeof(double), st));      // the slots past n_sol: zero
+    HIPCHK(hipMemsetAsync(dE.p, 0, (size_t)90 * n_sets * sizeof(double), dev.st));      // the slots past n_sol: zero
     EventTimer<1> ev;
-    if (g_relorient_timing) ev.start(st);
-    ro_launch_essmat5(st, n_sets, dss.p, dQ1.p, dQ2.p, nullptr, dE.p, dn.p);
-    ev.lap(st);
-    HIPCHK(hipMemcpy(E, dE.p, (size_t)90 * n_sets * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(n_sol, dn.p, (size_t)n_sets * sizeof(int32_t), hipMemcpyDeviceToHost));
-    g_relorient_ms[0] = ev.read(); g_relorient_ms[1] = g_relorient_ms[2] = 0;
+    RelorientClock::start(ev, dev.st);
+    ro_launch_essmat5(dev.st, n_sets, dss.p, dQ1.p, dQ2.p, nullptr, dE.p, dn.p);
+    ev.lap(dev.st);
+    dE.download(E); dn.download(n_sol);
+    RelorientClock::ms[0] = ev.read(); RelorientClock::ms[1] = RelorientClock::ms[2] = 0;
     return DBAT_HIP_OK;
     API_CATCH
 }
@@ -82,8 +74,8 @@ int dbat_hip_relorient(int32_t device, int32_t n_pairs, const int64_t *pt_start,
     if (given) hyp_start = no_hyp.data();
     if (n_pairs < 0 || !pt_start || !thr2 || !E || !P2 || !stats || !inlier || !in_front || !X) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
     if (front_dir != 1 && front_dir != -1) { g_err = "relorient: front_dir must be +1 or -1"; return DBAT_HIP_EINVAL; }
-    if (pt_start[0] != 0 || hyp_start[0] != 0) { g_err = "relorient: ranges must start at 0"; return DBAT_HIP_EINVAL; }
-    for (int32_t p = 0; p < n_pairs; ++p) {
+    check_ranges_start("relorient", pt_start); check_ranges_start("relorient", hyp_start);
+    for (int32_t p = 0; p < n_pairs; ++p) {            // (worded for the pairs: inline)
         const int64_t np_ = pt_start[p + 1] - pt_start[p], nh = hyp_start[p + 1] - hyp_start[p];
         if (np_ < 5) { g_err = "relorient: pair " + std::to_string(p) + " has fewer than five correspondences"; return DBAT_HIP_EINVAL; }
         if (nh < 0 || nh > 100000000) { g_err = "relorient: the sample ranges must ascend (at most 1e8 samples per pair)"; return DBAT_HIP_EINVAL; }
@@ -95,26 +87,22 @@ int dbat_hip_relorient(int32_t device, int32_t n_pairs, const int64_t *pt_start,
         for (int64_t i = 0; i < 9 * (int64_t)n_pairs; ++i)
             if (!std::isfinite(E[i])) { g_err = "relorient: a given E is not finite"; return DBAT_HIP_EINVAL; }
     if ((total > 0 && (!x1 || !x2)) || (S > 0 && !samples)) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    for (int64_t i = 0; i < 2 * total; ++i)
-        if (!std::isfinite(x1[i]) || !std::isfinite(x2[i])) { g_err = "relorient: correspondence " + std::to_string(i / 2) + " is not finite"; return DBAT_HIP_EINVAL; }
+    check_columns("relorient", "correspondence", 2, total, x1, x2);
     std::vector<int64_t> gidx((size_t)5 * S);
+    // (the sample checks of the three calls differ in order and wording, and this one runs over 5e5 samples: inline)
     for (int32_t p = 0; p < n_pairs; ++p) {
         const int64_t np_ = pt_start[p + 1] - pt_start[p];
         for (int64_t h = hyp_start[p]; h < hyp_start[p + 1]; ++h)
             for (int i = 0; i < 5; ++i) {
                 const int32_t q = samples[5 * h + i];
-                if (q < 0 || q >= np_) { g_err = "relorient: sample index outside the pair's correspondences"; return DBAT_HIP_EINVAL; }
+                if (q < 0 || q >= np_) refuse("relorient", "sample index outside the pair's correspondences");
                 for (int j = 0; j < i; ++j)
-                    if (samples[5 * h + j] == q) { g_err = "relorient: a sample repeats an index"; return DBAT_HIP_EINVAL; }
+                    if (samples[5 * h + j] == q) refuse("relorient", "a sample repeats an index");
                 gidx[(size_t)5 * h + i] = pt_start[p] + q;
             }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { g_err = "no HIP device: the dbat_hip core has no CPU path"; return DBAT_HIP_EDEVICE; }
-    if (device < 0 || device >= ndev) { g_err = "bad device index"; return DBAT_HIP_EINVAL; }
+    BatchDevice dev(device);
     if (n_pairs == 0) return DBAT_HIP_OK;
-    DeviceGuard dev_guard(device);
-    const hipStream_t st = nullptr;
     std::vector<int64_t> tile_start((size_t)n_pairs + 1, 0);
     for (int32_t p = 0; p < n_pairs; ++p) tile_start[p + 1] = tile_start[p] + cdiv(10 * (hyp_start[p + 1] - hyp_start[p]), RO_SCORE_WG);
     const int64_t n_tiles = tile_start[n_pairs];
@@ -129,25 +117,23 @@ int dbat_hip_relorient(int32_t device, int32_t n_pairs, const int64_t *pt_start,
     dE.alloc((size_t)90 * S); dn.alloc((size_t)S); dbest.alloc((size_t)n_pairs); dEw.alloc((size_t)9 * n_pairs); dwin.alloc((size_t)3 * n_pairs);
     dP4.alloc((size_t)48 * n_pairs); dcnt.alloc((size_t)4 * n_pairs); dsel.alloc((size_t)n_pairs);
     dX.alloc((size_t)3 * total); dfr.alloc((size_t)total); din.alloc((size_t)total);
-    HIPCHK(hipMemsetAsync(dbest.p, 0, (size_t)n_pairs * sizeof(unsigned long long), st));
-    HIPCHK(hipMemsetAsync(dcnt.p, 0, (size_t)4 * n_pairs * sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(dbest.p, 0, (size_t)n_pairs * sizeof(unsigned long long), dev.st));
+    HIPCHK(hipMemsetAsync(dcnt.p, 0, (size_t)4 * n_pairs * sizeof(int32_t), dev.st));
     EventTimer<2> e01;
     EventTimer<1> e2;
-    if (g_relorient_timing) e01.start(st);
-    if (S > 0) ro_launch_essmat5(st, S, nullptr, dx1.p, dx2.p, didx.p, dE.p, dn.p);
-    e01.lap(st);
-    if (n_tiles > 0) launch<k_ro_score>(dim3((unsigned)n_tiles), dim3(RO_SCORE_WG), 0, st, (int)n_pairs, dts.p, dps.p, dx1.p, dx2.p, dhs.p, dE.p, dn.p, dthr.p, dbest.p);
-    if (!given) launch<k_ro_winner>(dim3((unsigned)cdiv(n_pairs, 64)), dim3(64), 0, st, (int)n_pairs, dhs.p, dE.p, dbest.p, dEw.p, dwin.p);
-    e01.lap(st);
+    RelorientClock::start(e01, dev.st);
+    if (S > 0) ro_launch_essmat5(dev.st, S, nullptr, dx1.p, dx2.p, didx.p, dE.p, dn.p);
+    e01.lap(dev.st);
+    if (n_tiles > 0) launch<k_ro_score>(dim3((unsigned)n_tiles), dim3(RO_SCORE_WG), 0, dev.st, (int)n_pairs, dts.p, dps.p, dx1.p, dx2.p, dhs.p, dE.p, dn.p, dthr.p, dbest.p);
+    if (!given) launch<k_ro_winner>(dim3((unsigned)cdiv(n_pairs, 64)), dim3(64), 0, dev.st, (int)n_pairs, dhs.p, dE.p, dbest.p, dEw.p, dwin.p);
+    e01.lap(dev.st);
     std::vector<int32_t> win((size_t)3 * n_pairs, 0), nsol((size_t)S), cnt((size_t)4 * n_pairs), sel((size_t)n_pairs);
     std::vector<double> P4((size_t)48 * n_pairs);
     if (given) HIPCHK(hipMemcpy(dEw.p, E, (size_t)9 * n_pairs * sizeof(double), hipMemcpyHostToDevice));   // sample 0, solution 0
-    else {
-        HIPCHK(hipMemcpy(E, dEw.p, (size_t)9 * n_pairs * sizeof(double), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(win.data(), dwin.p, win.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    if (S > 0) HIPCHK(hipMemcpy(nsol.data(), dn.p, nsol.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    g_relorient_ms[0] = e01.read(); g_relorient_ms[1] = e01.ms[1];
+    else { dEw.download(E); dwin.download(win.data()); }
+    dn.download(nsol.data());                         // (empty without samples)
+    double *const ms = RelorientClock::ms;
+    ms[0] = e01.read(); ms[1] = e01.ms[1];
     const double nan = std::nan("");
     for (int32_t p = 0; p < n_pairs; ++p) {
         if (win[3 * p + 1] >= 0) ro_candidates(E + 9 * (size_t)p, P4.data() + 48 * (size_t)p);
@@ -155,9 +141,9 @@ int dbat_hip_relorient(int32_t device, int32_t n_pairs, const int64_t *pt_start,
     }
     HIPCHK(hipMemcpy(dP4.p, P4.data(), P4.size() * sizeof(double), hipMemcpyHostToDevice));
     const dim3 cgrid((unsigned)cdiv(total, 256));
-    if (g_relorient_timing) e2.start(st);
-    launch<k_ro_cams>(cgrid, dim3(256), 0, st, (int)n_pairs, dps.p, dx1.p, dx2.p, dP4.p, (const int32_t *)nullptr, dEw.p, dthr.p, (int)front_dir, dcnt.p, dX.p, dfr.p, din.p);
-    HIPCHK(hipMemcpy(cnt.data(), dcnt.p, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    RelorientClock::start(e2, dev.st);
+    launch<k_ro_cams>(cgrid, dim3(256), 0, dev.st, (int)n_pairs, dps.p, dx1.p, dx2.p, dP4.p, (const int32_t *)nullptr, dEw.p, dthr.p, (int)front_dir, dcnt.p, dX.p, dfr.p, din.p);
+    dcnt.download(cnt.data());
     for (int32_t p = 0; p < n_pairs; ++p) {
         int32_t *s = stats + 8 * (size_t)p;
         int64_t models = 0;
@@ -172,12 +158,10 @@ int dbat_hip_relorient(int32_t device, int32_t n_pairs, const int64_t *pt_start,
         for (int i = 0; i < 12; ++i) P2[12 * (size_t)p + i] = sel[p] >= 0 ? P4[48 * (size_t)p + 12 * sel[p] + i] : nan;
     }
     HIPCHK(hipMemcpy(dsel.p, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    launch<k_ro_cams>(cgrid, dim3(256), 0, st, (int)n_pairs, dps.p, dx1.p, dx2.p, dP4.p, (const int32_t *)dsel.p, dEw.p, dthr.p, (int)front_dir, dcnt.p, dX.p, dfr.p, din.p);
-    e2.lap(st);
-    HIPCHK(hipMemcpy(X, dX.p, (size_t)3 * total * sizeof(double), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(in_front, dfr.p, (size_t)total, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(inlier, din.p, (size_t)total, hipMemcpyDeviceToHost));
-    g_relorient_ms[2] = e2.read();
+    launch<k_ro_cams>(cgrid, dim3(256), 0, dev.st, (int)n_pairs, dps.p, dx1.p, dx2.p, dP4.p, (const int32_t *)dsel.p, dEw.p, dthr.p, (int)front_dir, dcnt.p, dX.p, dfr.p, din.p);
+    e2.lap(dev.st);
+    dX.download(X); dfr.download(in_front); din.download(inlier);
+    ms[2] = e2.read();
     if (given)                                        // the count of a given model: that of its mask
         for (int32_t p = 0; p < n_pairs; ++p) {
             int32_t c = 0;
@@ -192,10 +176,6 @@ int dbat_hip_relorient(int32_t device, int32_t n_pairs, const int64_t *pt_start,
  * bracket their kernels with device events (off by default); dbat_hip_debug_relorient_ms then gives the milliseconds
  * of the last call: ms[0] the solver, ms[1] scoring and winner, ms[2] the two decomposition passes (with the small
  * copies between them). */
-int dbat_hip_debug_relorient_timing(int32_t on) { g_relorient_timing = on != 0; return DBAT_HIP_OK; }
-int dbat_hip_debug_relorient_ms(double *ms) {
-    if (!ms) { g_err = "null argument"; return DBAT_HIP_EINVAL; }
-    for (int i = 0; i < 3; ++i) ms[i] = g_relorient_ms[i];
-    return DBAT_HIP_OK;
-}
+int dbat_hip_debug_relorient_timing(int32_t on) { return RelorientClock::set(on); }
+int dbat_hip_debug_relorient_ms(double *ms) { return RelorientClock::get(ms); }
 }  // extern "C"
