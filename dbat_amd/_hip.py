@@ -188,6 +188,10 @@ SYMBOLS = {
                                          _dp, _ip, _bp, _dp]),
     'dbat_hip_poseadjust': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _dp, _dp, _bp, _dp, C.POINTER(PairOptions), _dp,
                                       _bp, _dp, _ip, _dp, _dp]),
+    'dbat_hip_intersect_ransac': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _dp, C.c_int32, _dp, _bp,
+                                            C.POINTER(C.c_int64), _ip, _dp, C.c_double, _dp, _ip, _bp, _dp]),
+    'dbat_hip_pointadjust': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), _ip, _dp, C.c_int32, _dp, _bp, _dp,
+                                       C.POINTER(PairOptions), _dp, _bp, _dp, _ip, _dp, _dp]),
     'dbat_hip_bench_step': (C.c_int, [_H, C.c_double, C.c_int32, _dp]),
     'dbat_hip_structure_key': (C.c_int, [C.POINTER(Problem), C.POINTER(C.c_uint64)]),
     'dbat_hip_handle_key': (C.c_int, [_H, C.POINTER(C.c_uint64)]),
@@ -235,6 +239,8 @@ DEBUG_SYMBOLS = {
     'dbat_hip_debug_pairadjust_timing': (C.c_int, [C.c_int32]),
     'dbat_hip_debug_resect_robust_ms': (C.c_int, [_dp]),
     'dbat_hip_debug_resect_robust_timing': (C.c_int, [C.c_int32]),
+    'dbat_hip_debug_intersect_robust_ms': (C.c_int, [_dp]),
+    'dbat_hip_debug_intersect_robust_timing': (C.c_int, [C.c_int32]),
 }
 
 _lib = None
@@ -1141,6 +1147,75 @@ def resect_robust_ms():
     """Device-event milliseconds of the kernels of the last resect_ransac and poseadjust calls on this thread, after
     resect_robust_timing(True) (debug)."""
     return _kernel_ms('resect_robust', ('ransac', 'adjust'))
+
+
+def _rays(who, ray_start, cam, xn, P):
+    """The arguments dbat_hip_intersect_ransac and dbat_hip_pointadjust share: (n, total, n_cams, ray_start, cam, xn, P)."""
+    rs = np.ascontiguousarray(ray_start, np.int64)
+    n = len(rs) - 1
+    xn = np.asarray(xn, float)
+    cm = np.ascontiguousarray(np.asarray(cam, np.int32).reshape(-1))
+    P = np.asarray(P, float).reshape(-1, 3, 4)
+    if n < 0 or xn.ndim != 2 or xn.shape[0] != 2 or xn.shape[1] != rs[-1] or cm.size != xn.shape[1]:
+        raise ValueError('%s: xn must be 2-by-total and cam hold total indices, total the end of the last range' % who)
+    return n, xn.shape[1], P.shape[0], rs, cm, _f64(xn), _poses_in(P, P.shape[0])
+
+
+def intersect_ransac(ray_start, cam, xn, P, thr2, smp_start=None, samples=None, use=None, min_angle=0.0, device=0):
+    """dbat_hip_intersect_ransac over the points ray_start[i] .. ray_start[i + 1] of cam (total camera indices into P) and
+    the columns of xn (2-by-total), with the cameras P (n_cams, 3, 4: [R | -R C]), the thresholds thr2 (one per camera),
+    the samples smp_start[i] .. smp_start[i + 1] of the rows of samples (two indices local to the point each; smp_start
+    None, or an empty range: every pair of the point, enumerated on the device), the optional mask use (total booleans)
+    and min_angle in radians: dict(X (3, n), stats (n, 4: count, sample, hypotheses scored, usable rays), inlier (total),
+    ssq (n))."""
+    lib = load()
+    n, total, nc, rs, cm, xf, Pf = _rays('intersect_ransac', ray_start, cam, xn, P)
+    ss = None if smp_start is None else np.ascontiguousarray(smp_start, np.int64)
+    smp = np.ascontiguousarray(np.asarray(np.zeros((0, 2)) if samples is None else samples, np.int32).reshape(-1, 2))
+    t2 = np.ascontiguousarray(np.broadcast_to(np.asarray(thr2, float), (nc,)))
+    if (ss is not None and (len(ss) != n + 1 or smp.shape[0] != ss[-1])) or (ss is None and smp.shape[0] != 0):
+        raise ValueError('intersect_ransac: smp_start must hold one range per point and samples be k-by-2, k the end of the last range')
+    u = _mask(use, total)
+    X, st, ssq, inl = _out(n, 3), _out(n, 4, np.int32), _out(n), _out(total, 1, np.uint8)
+    check(lib.dbat_hip_intersect_ransac(int(device), n, _ptr(rs, _lp), _ptr(cm, _ip), dptr(xf), nc, dptr(Pf), _ptr(u, _bp),
+                                        _ptr(ss, _lp), _ptr(smp, _ip), dptr(t2), float(min_angle), dptr(X), _ptr(st, _ip),
+                                        _ptr(inl, _bp), dptr(ssq)))
+    return dict(X=X[:3 * n].reshape(3, n, order='F'), stats=st[:4 * n].reshape(n, 4), inlier=inl[:total].astype(bool), ssq=ssq[:n])
+
+
+def pointadjust(ray_start, cam, xn, P, X, use=None, w=None, max_iter=20, conv_tol=1e-6, min_angle=0.0, residuals=False, device=0):
+    """dbat_hip_pointadjust over the points ray_start[i] .. ray_start[i + 1] of cam and the columns of xn (2-by-total), with
+    the cameras P (n_cams, 3, 4), from the start points X (3-by-n); use (total booleans) and the weights w (2-by-total, or
+    anything that broadcasts to it) are optional.  Nothing given is changed.  Returns dict(X (3, n), used (total), f0, f,
+    sigma0, lam (n), code, iters, trials, n_used (n), Q (n, 3, 3), res (2, total; None unless residuals))."""
+    lib = load()
+    n, total, nc, rs, cm, xf, Pf = _rays('pointadjust', ray_start, cam, xn, P)
+    X = np.asarray(X, float)
+    if X.shape != (3, max(n, 0)):
+        raise ValueError('pointadjust: X must be 3-by-n, one start per point')
+    Xf = np.zeros(3) if n == 0 else X.flatten('F')
+    wt, u = _weights(w, total), _mask(use, total)
+    used, ds, ist, Q = _out(total, 1, np.uint8), _out(n, 4), _out(n, 4, np.int32), _out(n, 9)
+    res = _out(total, 2) if residuals else None
+    opt = PairOptions(int(max_iter), float(conv_tol), float(min_angle))
+    check(lib.dbat_hip_pointadjust(int(device), n, _ptr(rs, _lp), _ptr(cm, _ip), dptr(xf), nc, dptr(Pf), _ptr(u, _bp), dptr(wt),
+                                   C.byref(opt), dptr(Xf), _ptr(used, _bp), dptr(ds), _ptr(ist, _ip), dptr(Q), dptr(res)))
+    ds, ist = ds[:4 * n].reshape(n, 4), ist[:4 * n].reshape(n, 4)
+    return dict(X=Xf[:3 * n].reshape(3, n, order='F'), used=used[:total].astype(bool), f0=ds[:, 0].copy(), f=ds[:, 1].copy(),
+                sigma0=ds[:, 2].copy(), lam=ds[:, 3].copy(), code=ist[:, 0].copy(), iters=ist[:, 1].copy(), trials=ist[:, 2].copy(),
+                n_used=ist[:, 3].copy(), Q=Q[:9 * n].reshape(n, 3, 3).transpose(0, 2, 1),
+                res=None if res is None else res[:2 * total].reshape(total, 2).T)
+
+
+def intersect_robust_timing(on=True):
+    """Device events around the kernels of intersect_ransac / pointadjust calls on this thread (debug; off by default)."""
+    check(load().dbat_hip_debug_intersect_robust_timing(int(bool(on))))
+
+
+def intersect_robust_ms():
+    """Device-event milliseconds of the kernels of the last intersect_ransac and pointadjust calls on this thread, after
+    intersect_robust_timing(True) (debug)."""
+    return _kernel_ms('intersect_robust', ('ransac', 'adjust'))
 
 
 def rigidalign(X, Y, scale=False, use=None, resid=False, device=0):

@@ -35,6 +35,8 @@
 #include "pairadjust.hpp"
 #include "resect_ransac.hpp"
 #include "poseadjust.hpp"
+#include "intersect_ransac.hpp"
+#include "pointadjust.hpp"
 
 namespace dbat {
 
@@ -2017,3 +2019,4 @@ int dbat_hip_info(const dbat_hip_handle *h, int64_t *info) {
 #include "relorient_host.hpp"     // nor does the relative orientation
 #include "pairadjust_host.hpp"    // nor its least-squares refinement
 #include "poseadjust_host.hpp"    // nor the robust resection
+#include "intersect_host.hpp"     // nor the robust forward intersection

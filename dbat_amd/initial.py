@@ -17,6 +17,10 @@ control points and forward intersection of the object points, on
                    RANSAC over triples of control points scored by inlier count) and dbat_hip_poseadjust
                    (csrc/poseadjust.hpp k_poseadjust: the least-squares space resection on the winner's inliers, one wave
                    per camera); the reference has neither
+  forwintersect_robust, draw_pairs -> dbat_hip_intersect_ransac (csrc/intersect_ransac.hpp k_intersect_ransac: one wave per
+                   object point, a RANSAC over pairs of its image rays scored by inlier count) and dbat_hip_pointadjust
+                   (csrc/pointadjust.hpp k_pointadjust: the least-squares intersection on the winner's inliers, eight lanes
+                   per point); no handle; the reference has neither
   largesttriangle (misc/largesttriangle.m:16-41), derotmat3d (photogrammetry/derotmat3d.m:17-19), rotmat3d (its inverse),
   lenscorr1 (bundle/cammodel/pm_multilenscorr1.m:45-69 + pm_lens1.m:36-72), cleareo, clearop (misc/)
 
@@ -552,6 +556,194 @@ def resect_robust(s0, cams='all', cpId=None, n_hyp=256, thr_px=3.0, seed=0, refi
             fail = True
             s.EO.val[:6, ci] = np.nan
     return s, info, fail
+
+
+# ---- robust forward intersection ---------------------------------------------------------------------------------------
+
+def draw_pairs(n, n_hyp, rng):
+    """n_hyp rows of two distinct indices below n >= 2 from the generator rng, by the rule of draw_triples: rows with a
+    repeated index are drawn again until none is left (n < 16: the head of a permutation per row)."""
+    n, n_hyp = int(n), int(n_hyp)
+    if n < 2:
+        raise ValueError('draw_pairs: fewer than two rays')
+    if n < 16:
+        return np.array([rng.permutation(n)[:2] for _ in range(n_hyp)], np.int32).reshape(n_hyp, 2)
+    S = rng.integers(0, n, (n_hyp, 2))
+    while True:
+        bad = np.flatnonzero(S[:, 0] == S[:, 1])
+        if bad.size == 0:
+            return S.astype(np.int32)
+        S[bad] = rng.integers(0, n, (bad.size, 2))
+
+
+def _pair_of_number(k, r):
+    """The pair (i, j), i < j, that is number k = i (2 r - i - 1) / 2 + (j - i - 1) of the pairs of r rays (arrays)."""
+    k, r = np.asarray(k, np.int64), np.asarray(r, np.int64)
+    i = np.zeros_like(k)
+    rest = k.copy()
+    while True:
+        more = rest >= r - 1 - i
+        if not more.any():
+            return i, i + 1 + rest
+        rest = np.where(more, rest - (r - 1 - i), rest)
+        i = i + more
+
+
+MAX_EXHAUSTIVE_RAYS = 64                # IR_MAX_EXHAUSTIVE of csrc/intersect_ransac.hpp: rays up to which the device enumerates the pairs
+
+
+def pair_plan(r, n_hyp, rng):
+    """The samples of points of r rays each (an array): (ns, smp_start, smp).  A point with r (r - 1) / 2 <= n_hyp and at
+    most MAX_EXHAUSTIVE_RAYS rays brings none -- ns = 0: the device enumerates its pairs --, every other point of two rays
+    or more n_hyp pairs from draw_pairs(r, n_hyp, rng), point after point."""
+    r = np.asarray(r, np.int64)
+    heavy = np.flatnonzero((r * (r - 1) // 2 > int(n_hyp)) | (r > MAX_EXHAUSTIVE_RAYS))
+    ns = np.zeros(r.size, np.int64)
+    ns[heavy] = int(n_hyp)
+    smp = np.concatenate([draw_pairs(r[p], n_hyp, rng) for p in heavy], 0) if heavy.size and int(n_hyp) > 0 else np.zeros((0, 2), np.int32)
+    return ns, np.concatenate([[0], np.cumsum(ns)]), smp
+
+
+def point_rays(s0, pts):
+    """The image rays of the object points pts (columns of OP, ascending), point-major, as dbat_hip_intersect_ransac and
+    dbat_hip_pointadjust take them: (cols, ray_pt, r, ray_start, cam, xn, w, thr, P) -- the columns of IP in the order of
+    the points, the place in pts of every ray's point, the rays per point and their ranges, the camera of every ray, the
+    lens-corrected coordinates normalised as camera_points does (K \\ [x; y; 1] with -f), the weights
+    |f| / (pxSize IP.std), one pixel in normalised units per camera (mean(pxSize) / |f|) and the poses [R | -R C] of EO."""
+    pts = np.asarray(pts)
+    n = pts.size
+    npnt = s0.OP.val.shape[1]
+    ipcam, ippt = np.asarray(s0.IP.cam), np.asarray(s0.IP.pt)
+    do = np.zeros(npnt, bool)
+    do[pts] = True
+    # the rays, point-major: the columns of IP of the chosen points in the order of the points
+    sel = np.flatnonzero(do[ippt])
+    cols = sel[np.argsort(ippt[sel], kind='stable')]
+    where = np.full(npnt, -1)
+    where[pts] = np.arange(n)
+    ray_pt = where[ippt[cols]]
+    r = np.bincount(ray_pt, minlength=n)
+    ray_start = np.concatenate([[0], np.cumsum(r)])
+    cam = ipcam[cols]
+    nc = s0.EO.val.shape[1]
+    IO = s0.IO.val
+    xy = lenscorr1(s0)[:, cols]
+    xn = np.stack([(xy[0] - IO[1, cam]) / -IO[0, cam], (xy[1] - IO[2, cam]) / -IO[0, cam]])
+    px = np.asarray(s0.IO.sensor.pxSize, float)
+    thr = np.mean(px, 0) / np.abs(IO[0])                 # per camera
+    if getattr(s0.IO.sensor, 'samePxSize', False):
+        px = np.tile(px[0], (2, 1))
+    w = np.abs(IO[0, cam]) / (px[:, cam] * np.asarray(s0.IP.std, float)[:, cols])
+    P = np.stack([np.hstack([R, -(R @ s0.EO.val[:3, i])[:, None]]) for i in range(nc) for R in (rotmat3d(s0.EO.val[3:6, i]),)])
+    return cols, ray_pt, r, ray_start, cam, xn, w, thr, P
+
+
+def forwintersect_robust(s0, ids='all', skipPrior=False, n_hyp=256, thr_px=3.0, min_angle_deg=0.0, min_count=2, seed=0, refine=True,
+                         reselect=0, max_iter=20, conv_tol=1e-6, device=0):
+    """Robust forward intersection of the object points: (s, info, fail).  The image points are lens-corrected and
+    normalised as camera_points does (lenscorr1, K \\ [x; y; 1] with -f), the poses [R | -R C] come from EO (rotmat3d), and
+    one device call (dbat_hip_intersect_ransac) intersects pairs of rays of every point and returns the hypothesis with the
+    most rays within thr_px pixels -- thr_px mean(pxSize) / |f| in normalised units, per camera -- among those whose rays
+    meet at min_angle_deg or more.  A point of r rays with r (r - 1) / 2 <= n_hyp has every pair tried (enumerated on the
+    device); the others, and every point of more than 64 rays, get n_hyp pairs from draw_pairs with
+    np.random.default_rng(seed), point after point (pair_plan).  With refine
+    the inliers of every winner go through the least-squares intersection (dbat_hip_pointadjust, all points in one call)
+    with the weights |f| / (pxSize IP.std); every one of `reselect` rounds then thresholds the residuals of all the point's
+    rays at the refined point again and refines on the new inliers, where they are not fewer and the adjustment
+    converges.  No handle is created.  ids and skipPrior choose the points as in forwintersect(); the others keep their
+    values.  info is a dict of arrays, one entry per chosen point (info['pts']: its column of OP) unless noted:
+      count, n_rays        the inliers and the rays of the point
+      sample               the winning pair as two columns of IP, -1 without a winner
+      sigma0, Q            of the refinement: sqrt(f / (2 count - 3)) and the 3-by-3 cofactor matrix; NaN without refine
+      code, iters          of the refinement (0 converged / 1 max_iter / 2 no step / 3 singular); 0 without refine
+      rms_px               the rms over the inliers of the residual in pixels
+      inlier               over the columns of IP: the rays that agree with their point
+    A point without a winner, or with count < min_count, becomes NaN with code -1, and fail is True."""
+    from . import _hip
+    from .dbatstruct import copy_struct
+    if not np.all(np.isfinite(s0.EO.val)):
+        raise ValueError('Bad or uninitialized EO data')
+    if not np.all(np.isfinite(s0.IO.val)):
+        raise ValueError('Bad or uninitialized IO data')
+    s = copy_struct(s0)
+    npnt = s0.OP.val.shape[1]
+    do = np.ones(npnt, bool) if isinstance(ids, str) and ids == 'all' else np.isin(s0.OP.id, ids)
+    if skipPrior:
+        do &= np.all(s0.bundle.est.OP, 0) & ~np.any(s0.prior.OP.use, 0)
+    pts = np.flatnonzero(do)
+    n = pts.size
+    nan = np.nan
+    info = dict(pts=pts, count=np.zeros(n, int), n_rays=np.zeros(n, int), sample=np.full((n, 2), -1), sigma0=np.full(n, nan),
+                Q=np.full((n, 3, 3), nan), code=np.full(n, -1), iters=np.zeros(n, int), rms_px=np.full(n, nan),
+                inlier=np.zeros(np.asarray(s0.IP.cam).size, bool))
+    if n == 0:
+        return s, info, False
+    cols, ray_pt, r, ray_start, cam, xn, w, thr, P = point_rays(s0, pts)
+    thr = float(thr_px) * thr
+    ns, smp_start, smp = pair_plan(r, n_hyp, np.random.default_rng(seed))
+    a = _hip.intersect_ransac(ray_start, cam, xn, P, thr ** 2, smp_start=smp_start if smp.shape[0] else None, samples=smp,
+                              min_angle=np.deg2rad(float(min_angle_deg)), device=device)
+    st = a['stats']
+    won = st[:, 1] >= 0
+    X, inl = a['X'].copy(), a['inlier'].copy()
+    info['count'], info['n_rays'] = st[:, 0].astype(int), r
+    info['code'] = np.where(won, 0, -1)
+    i, j = _pair_of_number(np.where(won & (ns == 0), st[:, 1], 0), np.maximum(r, 2))
+    listed = np.flatnonzero(won & (ns > 0))
+    i[listed], j[listed] = smp[smp_start[listed] + st[listed, 1]].T
+    ww = np.flatnonzero(won)
+    info['sample'][ww] = np.stack([cols[ray_start[ww] + i[ww]], cols[ray_start[ww] + j[ww]]], 1)
+
+    def e2_front(Xc):
+        """(the squared residual in normalised units, whether the point is in front) of every ray at the points Xc."""
+        with np.errstate(all='ignore'):
+            Pr = P[cam]
+            h = np.einsum('rij,jr->ir', Pr[:, :, :3], Xc[:, ray_pt]) + Pr[:, :, 3].T
+            e = h[:2] / h[2] - xn
+            return np.sum(e * e, 0), h[2] < 0
+
+    def adjust(which, use):
+        """pointadjust of the points `which` on the rays `use` (over all rays), from their current values."""
+        pick = np.isin(ray_pt, which)
+        rs = np.concatenate([[0], np.cumsum(r[which])])
+        b = _hip.pointadjust(rs, cam[pick], xn[:, pick], P, X[:, which], use=use[pick], w=w[:, pick], max_iter=max_iter,
+                             conv_tol=conv_tol, device=device)
+        return b, pick
+
+    def take(which, b, pick, ok):
+        """The refinements b of the points which[ok] become their results."""
+        k = which[ok]
+        X[:, k] = b['X'][:, ok]
+        for key, src in (('count', 'n_used'), ('sigma0', 'sigma0'), ('Q', 'Q'), ('code', 'code'), ('iters', 'iters')):
+            info[key][k] = b[src][ok]
+        rays_ok = np.isin(ray_pt[pick], k)
+        inl[np.flatnonzero(pick)[rays_ok]] = b['used'][rays_ok]
+
+    if refine and won.any():
+        which = np.flatnonzero(won)
+        b, pick = adjust(which, inl)
+        take(which, b, pick, b['code'] != 4)
+        for _ in range(int(reselect)):
+            e2, front = e2_front(X)
+            mask = front & (e2 <= thr[cam] ** 2) & np.isfinite(e2)
+            cnt = np.bincount(ray_pt, weights=mask, minlength=n).astype(int)
+            changed = np.bincount(ray_pt, weights=mask != inl, minlength=n) > 0
+            which = np.flatnonzero((info['code'] >= 0) & (info['code'] != 4) & changed & (cnt >= info['count']))
+            if which.size == 0:
+                break
+            b, pick = adjust(which, mask)
+            take(which, b, pick, (b['code'] == 0) & (b['n_used'] >= info['count'][which]))
+    bad = ~won | (info['count'] < int(min_count))
+    X[:, bad] = nan
+    info['code'][bad] = -1
+    inl[bad[ray_pt]] = False
+    e2, _ = e2_front(X)
+    with np.errstate(all='ignore'):
+        ssq_px = np.bincount(ray_pt, weights=np.where(inl, e2 / thr[cam] ** 2, 0.0), minlength=n) * float(thr_px) ** 2
+        info['rms_px'] = np.where(bad, nan, np.sqrt(ssq_px / np.maximum(info['count'], 1)))
+    info['inlier'][cols] = inl
+    s.OP.val[:, pts] = X
+    return s, info, bool(bad.any())
 
 
 resect_hip = resect                   # (names of rounds 2-3)

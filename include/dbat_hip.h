@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DBAT_HIP_ABI_VERSION 5   /* 5: dbat_hip_redundancy; additive: dbat_hip_robust_weights / dbat_hip_set_obs_weights / dbat_hip_solve_robust; 4: dbat_hip_options grew (trace_fun); dbat_hip_structure_key / dbat_hip_handle_key / dbat_hip_set_values; dbat_hip_bench_step ms[16], dbat_hip_info [24]; 3: dbat_hip_options grew (term_fun, veto_fun); 2: dbat_hip_result grew (stage_s, n_trace_only); dbat_hip_info [16]; dbat_hip_bench_step ms[12] */
+#define DBAT_HIP_ABI_VERSION 5   /* 5: dbat_hip_redundancy; additive: dbat_hip_robust_weights / dbat_hip_set_obs_weights / dbat_hip_solve_robust, dbat_hip_intersect_ransac / dbat_hip_pointadjust; 4: dbat_hip_options grew (trace_fun); dbat_hip_structure_key / dbat_hip_handle_key / dbat_hip_set_values; dbat_hip_bench_step ms[16], dbat_hip_info [24]; 3: dbat_hip_options grew (term_fun, veto_fun); 2: dbat_hip_result grew (stage_s, n_trace_only); dbat_hip_info [16]; dbat_hip_bench_step ms[12] */
 
 /* error returns */
 #define DBAT_HIP_OK            0
@@ -639,6 +639,90 @@ int  dbat_hip_resect_ransac(int32_t device, int32_t n_images, const int64_t *pt_
 int  dbat_hip_poseadjust(int32_t device, int32_t n_images, const int64_t *pt_start, const double *X, const double *xn,
                          const uint8_t *use, const double *w, const dbat_hip_pair_options *opt, double *P, uint8_t *used,
                          double *dstat, int32_t *istat, double *Q, double *res);
+
+/* ---- robust forward intersection (additive to ABI 5; csrc/intersect_ransac.hpp, csrc/pointadjust.hpp) -------- */
+
+/* Forward intersection of n_points object points by a RANSAC over pairs of their image rays, in one call.  The reference
+ * has no counterpart: pm_forwintersect3.m:55-82 is one linear solve over all rays of a point, so that one mismatched image
+ * measurement drags the point away (dbat_hip_forwintersect above keeps that behaviour).  No handle, no plan.
+ *   ray_start [n_points+1]  range of every point's rays in cam / xn / use / inlier; a point may have none
+ *   cam       [total]       the index of the ray's camera in P and thr2
+ *   xn        [2*total]     lens-corrected, normalised image coordinates with the conventions of dbat_hip_resect_ransac:
+ *                           K \ [x; y; 1] with -f, so that the cameras look along -z, and a point is in front where the
+ *                           third row of P [X; 1] is negative
+ *   n_cams, P [12*n_cams]   the cameras: [R | -R C], column-major 3 x 4
+ *   use       [total]       or NULL (all): the rays that may be sampled and counted
+ *   smp_start [n_points+1]  or NULL: range of every point's samples in smp.  A point whose range is empty -- every point
+ *                           when smp_start is NULL -- has all its pairs enumerated on the device, lexicographically over
+ *                           i < j: sample k = i (2 r - i - 1) / 2 + (j - i - 1) of its r rays.  That is allowed up to
+ *                           64 rays (2016 pairs); a point of more must bring samples
+ *   smp       [2*samples]   two distinct indices into the point's ray range per sample: drawn by the caller, so the call
+ *                           is deterministic
+ *   thr2      [n_cams]      inlier threshold on the squared residual, in normalised units, per camera (focal lengths
+ *                           differ)
+ *   min_angle               in [0, pi/2): a pair of rays that meet at a smaller angle is not scored
+ *   X         [3*n_points]  out: the winning point, NaN without a winner
+ *   stats     [4*n_points]  out: the inlier count, the winning sample (local to the point: its place in smp, or k above),
+ *                           the number of hypotheses scored, the number of usable rays; count 0 and sample -1 without a
+ *                           winner
+ *   inlier    [total]       out: 1 where the ray is an inlier of the returned X; all zero without a winner
+ *   ssq       [n_points]    out: the sum of e0^2 + e1^2 over the inliers; 0 without a winner
+ * One wave per point, four points per workgroup; a lane takes one sample.  A hypothesis is the middle of the common
+ * perpendicular of its two rays (centre -R' t, direction R' (x0, x1, 1), normalised): what pm_forwintersect3.m:55-68
+ * gives for two rays.  It is scored only if both rays may be used, |d1 x d2|^2 >= max(sin^2 min_angle, 1e-24) on the unit
+ * directions, and the point is finite.  A ray is an inlier if use is set, the point is in front of its camera, and
+ * e0^2 + e1^2 <= thr2[cam] with e = pi(P [X; 1]) - xn evaluated in twice the working precision, as
+ * dbat_hip_resect_ransac scores.  The winner has the highest count and needs at least 2; of equal counts the lowest
+ * sample wins.  Counts are integers and the winner is one integer maximum: no floating-point atomics, two calls give the
+ * same bits, and a point gives the same bits alone and in a batch.
+ * DBAT_HIP_EINVAL, before any device call, in this order: a null argument; negative counts; ranges (ray_start, then
+ * smp_start) that do not ascend from 0; cam outside [0, n_cams); an xn of a usable ray, or a P, that is not finite; an R with |R'R - I| > 1e-6 or
+ * det R < 0; thr2 not positive and finite; min_angle outside [0, pi/2); a sample index out of range or repeated inside its
+ * sample; a point with no samples and more than 64 rays; 2^29 rays or 2^31 samples and more in one point.  Then
+ * DBAT_HIP_EDEVICE without a HIP device (no CPU path).  n_points = 0 returns DBAT_HIP_OK. */
+int  dbat_hip_intersect_ransac(int32_t device, int32_t n_points, const int64_t *ray_start, const int32_t *cam, const double *xn,
+                               int32_t n_cams, const double *P, const uint8_t *use, const int64_t *smp_start, const int32_t *smp,
+                               const double *thr2, double min_angle, double *X, int32_t *stats, uint8_t *inlier, double *ssq);
+
+/* Least-squares forward intersection of n_points object points in one call: every point from its image rays, minimising
+ * sum |w (pi(R (X - C)) - xn)|^2 over the used rays, with sigma0 and the cofactor matrix.  No handle, no plan; a group of
+ * eight lanes per point runs the whole damped loop.  The reference has no counterpart: it reaches this point only through
+ * bundle.m on a project with every camera fixed.
+ *   ray_start, cam, xn, n_cams, P   as dbat_hip_intersect_ransac
+ *   use       [total]       or NULL (all): rays that may be used
+ *   w         [2*total]     or NULL (ones): weights per coordinate, the reciprocal standard deviations in normalised units
+ *   opt                     max_iter and conv_tol of dbat_hip_pair_options, with its defaults; min_angle must be 0
+ *   X         [3*n_points]  in/out; the start of a point that has a ray to use must be finite
+ *   used      [total]       out: the rays used, chosen once at the start point: use is set and the point is in front
+ *   dstat     [4*n_points]  out: the objective at the start, the objective, sigma0, lambda
+ *   istat     [4*n_points]  out: code, iterations (accepted steps), trials, n (the rays used)
+ *   Q         [9*n_points]  out: cofactor matrix, 3 x 3 column-major: the inverse of the undamped normal matrix at the
+ *                           returned point.  The covariance is sigma0^2 Q
+ *   res       [2*total]     out, or NULL: weighted residuals at the returned point of every finite ray, used or not (a
+ *                           caller can threshold them and call again); zero where they are not finite, and for a point
+ *                           that ends with code 4
+ * The damping loop is that of dbat_hip_poseadjust point for point: Levenberg-Marquardt with Marquardt's scaling
+ * (lambda diag N), lambda from 1e-3, lambda <- max(lambda / 10, 1e-12) on an accepted trial, 10 lambda on a rejected one
+ * (the same linearisation is solved again), the end above 1e8; a trial is accepted if its objective is finite and smaller
+ * and every used ray is still in front; every trial tests for the end first: q <= conv_tol^2 f with q = -g' delta, or
+ * f <= 1e-24 * 2 n.  The normal equations are float64; the objective of the accept test is formed and summed in pairs of
+ * doubles, and the returned f is the high word.  Coordinates are taken relative to the projection centre of the point's
+ * first used ray before anything is multiplied: coordinates of 1e6 m keep their digits.
+ * Codes: 0 converged; 1 max_iter steps done; 2 no acceptable step before lambda > 1e8; 3 converged, but the undamped
+ * matrix has a Cholesky pivot <= 1e-10 of its diagonal entry (near-parallel rays): Q is NaN; 4 fewer than two rays used: X
+ * is returned as given, dstat is NaN but for lambda, Q is NaN.  sigma0 = sqrt(f / (2 n - 3)).  Q is NaN for every singular
+ * end, whatever the code.  Nothing else returned is ever non-finite.  The sums have a fixed shape and there are no atomics:
+ * two calls give the same bits, and a point gives the same bits alone and in a batch, wherever it lands in a wave.
+ * DBAT_HIP_EINVAL, before any device call: a null argument; negative counts; max_iter outside 1 .. 200; conv_tol <= 0;
+ * min_angle != 0; a ray_start that does not ascend from 0; cam outside [0, n_cams); an xn of a usable ray that is not
+ * finite; 2^29 rays and more in one point; an X of a point with a usable ray that is not finite; a weight that is not
+ * positive and finite; a P that is not finite or whose R is not a rotation.  Then DBAT_HIP_EDEVICE without a HIP device
+ * (no CPU path).  What the data of one point cause -- too few rays, no convergence, singularity -- is that point's code,
+ * never an error. */
+int  dbat_hip_pointadjust(int32_t device, int32_t n_points, const int64_t *ray_start, const int32_t *cam, const double *xn,
+                          int32_t n_cams, const double *P, const uint8_t *use, const double *w,
+                          const dbat_hip_pair_options *opt, double *X, uint8_t *used, double *dstat, int32_t *istat,
+                          double *Q, double *res);
 
 /* ---- measurement hooks -------------------------------------------------- */
 
