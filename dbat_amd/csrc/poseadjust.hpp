@@ -1,6 +1,6 @@
 // Least-squares space resection of camera stations (dbat_hip_poseadjust, host side: poseadjust_host.hpp): the pose of a
 // camera from its control points, for many cameras in one launch.  One wave of 64 lanes per camera; the whole damped
-// loop runs inside the kernel, as in pairadjust.hpp, whose protocol this follows point for point.
+// loop runs inside the kernel, by the protocol of lm_core.hpp.
 //
 // Unknowns of a camera: R and the projection centre C.  With pi(Y) = Y(1:2) / Y(3) the residuals of a point are
 // w (pi(R (X - C)) - xn).  A step is (c, a): C <- C + c, R <- exp([a]x) R: six unknowns, centre first.  The 6 x 6 normal
@@ -8,105 +8,44 @@
 // to the camera's first used point before anything is multiplied, so coordinates of 1e6 m keep their digits.
 //
 // Lane l takes the points l, l + 64, ... in ascending order; the 27 sums of the normal equations (21 of the symmetric
-// matrix, 6 of the gradient) and the objective, a pair of doubles, are reduced by a shuffle tree of fixed shape and
-// handed to every lane from lane 0.  Every lane then solves the same 6 x 6 system and takes the same decisions: the
-// loop has no workgroup barrier and no LDS, and its trip count is the same in every lane by construction.  The
-// linearisation does not depend on lambda, so a rejected trial solves the sums it has again.  No atomics: two calls
-// give the same bits, and a camera gives the same bits alone and inside a batch.
+// matrix, 6 of the gradient) and the objective, a pair of doubles, are reduced by __shfl_xor of width 64: a tree of fixed
+// shape that leaves the result in every lane (grp_sum of lm_core.hpp), every shuffle in control flow that is uniform over
+// the wave.  Every lane then solves the same 6 x 6 system and takes the same decisions: the loop has no workgroup barrier
+// and no LDS, and its trip count is the same in every lane by construction.  The linearisation does not depend on lambda,
+// so a rejected trial solves the sums it has again.  No atomics: two calls give the same bits, and a camera gives the
+// same bits alone and inside a batch.
 //
-// Every loop is bounded: the trial loop by PA_MAX_REJECT * max_iter (max_iter is validated to 1 .. 200 by the host),
+// Every loop is bounded: the trial loop by LM_MAX_REJECT * max_iter (max_iter is validated to 1 .. 200 by the host),
 // the point loops by the camera's size.  No array is indexed by a run-time value: everything below unrolls.
 #pragma once
-#include "pairadjust.hpp"
+#include "lm_core.hpp"
 #include "resect.hpp"
 
 namespace dbat {
 
 constexpr int PO_WAVE = 64;
-constexpr int PO_NSUM = 27;                 // N (21, po_s6 storage), g (6)
-constexpr double PO_PIVOT = 1e-10;          // at the end: a pivot of the undamped N at or below this share of its diagonal entry: singular
+constexpr int PO_NSUM = 27;                 // N (21, sym_ix<6> storage), g (6)
 constexpr int PO_MIN_POINTS = 3;
-
-__host__ __device__ constexpr int po_s6(int i, int j) { return i <= j ? i * 6 - i * (i - 1) / 2 + (j - i) : j * 6 - j * (j - 1) / 2 + (i - j); }
 
 #if defined(__HIPCC__)
 
-// Cholesky of the 6 x 6 matrix S (po_s6 storage) in place, unrolled: false where a pivot is not above tol times its
-// diagonal entry (the pivot is then replaced by one, as pa_chol5 does).
-__device__ __forceinline__ bool po_chol6(double *S, double tol) {
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const double sjj = S[po_s6(j, j)];
-        double d = sjj;
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= S[po_s6(k, j)] * S[po_s6(k, j)];
-        if (!(d > tol * sjj)) { ok = false; d = 1.0; }
-        const double l = sqrt(d);
-        S[po_s6(j, j)] = l;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = S[po_s6(j, i)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= S[po_s6(k, i)] * S[po_s6(k, j)];
-            S[po_s6(j, i)] = v / l;
-        }
-    }
-    return ok;
-}
-
-// x <- (L L')^-1 x with the factor of po_chol6 (L(i, j) at po_s6(j, i), j <= i).
-__device__ __forceinline__ void po_solve6(const double *L, double *x) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = x[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= L[po_s6(k, i)] * x[k];
-        x[i] = v / L[po_s6(i, i)];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = x[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) v -= L[po_s6(i, k)] * x[k];
-        x[i] = v / L[po_s6(i, i)];
-    }
-}
-
-// The wave's sum in lane 0 by a shuffle tree, then to every lane.
-__device__ __forceinline__ double po_wave_sum(double s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    return __shfl(s, 0, 64);
-}
-__device__ __forceinline__ PaDD po_wave_sum_dd(PaDD v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = pa_dd_add(v, PaDD{__shfl_down(v.hi, off, 64), __shfl_down(v.lo, off, 64)});
-    return PaDD{__shfl(v.hi, 0, 64), __shfl(v.lo, 0, 64)};
-}
-__device__ __forceinline__ long long po_wave_min(long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const long long o = __shfl_down(v, off, 64); v = o < v ? o : v; }
-    return __shfl(v, 0, 64);
-}
-
 // Y = R ((X - O) - C) as pairs of doubles (R: 18 entries, the low words from [9]; C relative to O) and the weighted
-// residuals rr = w ((Y_k - xn_k Y_3) / Y_3): the form of pa_residuals.  X - O is taken without error.
+// residuals rr = w ((Y_k - xn_k Y_3) / Y_3): the form of pa_residuals (pairadjust.hpp).  X - O is taken without error.
 __device__ __forceinline__ void po_residuals(const double *R, const double *C, const double *O, const double *X, const double *m,
-                                             const double *w, PaDD *Y, PaDD *rr) {
-    PaDD d[3];
+                                             const double *w, Dd *Y, Dd *rr) {
+    Dd d[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) d[k] = pa_dd_add(pa_two_sum(X[k], -O[k]), PaDD{-C[k], 0.0});
+    for (int k = 0; k < 3; ++k) d[k] = dd_add(dd_two_sum(X[k], -O[k]), Dd{-C[k], 0.0});
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        PaDD v = pa_dd_mul(PaDD{R[k], R[9 + k]}, d[0]);
-        v = pa_dd_add(v, pa_dd_mul(PaDD{R[3 + k], R[12 + k]}, d[1]));
-        Y[k] = pa_dd_add(v, pa_dd_mul(PaDD{R[6 + k], R[15 + k]}, d[2]));
+        Dd v = dd_mul(Dd{R[k], R[9 + k]}, d[0]);
+        v = dd_add(v, dd_mul(Dd{R[3 + k], R[12 + k]}, d[1]));
+        Y[k] = dd_add(v, dd_mul(Dd{R[6 + k], R[15 + k]}, d[2]));
     }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const PaDD b = pa_dd_fma(Y[k], -m[k], Y[2]);
-        rr[k] = pa_dd_fma(PaDD{0.0, 0.0}, w[k], pa_dd_div(b, Y[2]));
+        const Dd b = dd_fma(Y[k], -m[k], Y[2]);
+        rr[k] = dd_fma(Dd{0.0, 0.0}, w[k], dd_div(b, Y[2]));
     }
 }
 
@@ -126,30 +65,68 @@ __device__ __forceinline__ void po_jacobian(const double *R, const double *Y, co
     }
 }
 
-// The sums N (po_s6), g of the wave's used points at (R, C), in every lane.
+// Point g: its coordinates, its image point m and the weights w, ones where none are given.
+struct PoObs { double X[3], m[2], w[2]; };
+__device__ __forceinline__ PoObs po_load(int64_t g, const double *__restrict__ X, const double *__restrict__ xn, const double *__restrict__ wt) {
+    return {{X[3 * g], X[3 * g + 1], X[3 * g + 2]}, {xn[2 * g], xn[2 * g + 1]}, {wt ? wt[2 * g] : 1.0, wt ? wt[2 * g + 1] : 1.0}};
+}
+
+// acc[0 .. 20] += A' A of the point's two rows (sym_ix<6> storage)
+__device__ __forceinline__ void po_add_normal(const double *A, double *acc) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int c = a; c < 6; ++c) acc[sym_ix<6>(a, c)] += A[a] * A[c] + A[6 + a] * A[6 + c];
+}
+
+// The sums N, g of the wave's used points at (R, C), in every lane.  END, the pass at the returned values: N alone, and the
+// residuals of every finite point, used or not, to res (if not null).
+template <bool END>
 __device__ __forceinline__ void po_linearise(const double *R, const double *C, const double *O, int64_t g0, int64_t g1, int lane,
                                              const double *__restrict__ X, const double *__restrict__ xn, const double *__restrict__ wt,
-                                             const uint8_t *__restrict__ used, double *acc) {
+                                             const uint8_t *__restrict__ used, double *__restrict__ res, double *acc) {
+    constexpr int NS = END ? 21 : PO_NSUM;
 #pragma unroll
-    for (int i = 0; i < PO_NSUM; ++i) acc[i] = 0.0;
+    for (int i = 0; i < NS; ++i) acc[i] = 0.0;
     for (int64_t g = g0 + lane; g < g1; g += PO_WAVE) {
-        if (!used[g]) continue;
-        const double Xg[3] = {X[3 * g], X[3 * g + 1], X[3 * g + 2]}, m[2] = {xn[2 * g], xn[2 * g + 1]};
-        const double w[2] = {wt ? wt[2 * g] : 1.0, wt ? wt[2 * g + 1] : 1.0};
-        PaDD Y[3], rr[2];
-        po_residuals(R, C, O, Xg, m, w, Y, rr);
+        const bool u = used[g] != 0;
+        if (!u && !(END && res)) continue;
+        const PoObs o = po_load(g, X, xn, wt);
+        Dd Y[3], rr[2];
+        po_residuals(R, C, O, o.X, o.m, o.w, Y, rr);
+        if (END && res) {
+            const bool fin = (rr[0].hi - rr[0].hi == 0.0) && (rr[1].hi - rr[1].hi == 0.0);
+            res[2 * g] = fin ? rr[0].hi : 0.0; res[2 * g + 1] = fin ? rr[1].hi : 0.0;
+        }
+        if (!u) continue;
         const double Yh[3] = {Y[0].hi, Y[1].hi, Y[2].hi};
         double A[12];
-        po_jacobian(R, Yh, w, A);
+        po_jacobian(R, Yh, o.w, A);
+        po_add_normal(A, acc);
 #pragma unroll
-        for (int a = 0; a < 6; ++a) {
-#pragma unroll
-            for (int c = a; c < 6; ++c) acc[po_s6(a, c)] += A[a] * A[c] + A[6 + a] * A[6 + c];
-            acc[21 + a] += A[a] * rr[0].hi + A[6 + a] * rr[1].hi;
-        }
+        for (int a = 0; a < (END ? 0 : 6); ++a) acc[21 + a] += A[a] * rr[0].hi + A[6 + a] * rr[1].hi;
     }
 #pragma unroll
-    for (int i = 0; i < PO_NSUM; ++i) acc[i] = po_wave_sum(acc[i]);
+    for (int i = 0; i < NS; ++i) acc[i] = grp_sum<PO_WAVE>(acc[i]);
+}
+
+// The objective of the wave's used points at (R, C) (a pair of doubles) and the number of them that are not in front.
+__device__ __forceinline__ Dd po_objective(const double *R, const double *C, const double *O, int64_t g0, int64_t g1, int lane,
+                                           const double *__restrict__ X, const double *__restrict__ xn, const double *__restrict__ wt,
+                                           const uint8_t *__restrict__ used, double &nbad) {
+    Dd f = {0.0, 0.0};
+    double bad = 0.0;
+    for (int64_t g = g0 + lane; g < g1; g += PO_WAVE) {
+        if (!used[g]) continue;
+        const PoObs o = po_load(g, X, xn, wt);
+        Dd Y[3], rr[2];
+        po_residuals(R, C, O, o.X, o.m, o.w, Y, rr);
+        f = dd_add(f, dd_mul(rr[0], rr[0]));
+        f = dd_add(f, dd_mul(rr[1], rr[1]));
+        if (!(Y[2].hi < 0.0)) bad += 1.0;
+    }
+    nbad = grp_sum<PO_WAVE>(bad);
+    return grp_sum_dd<PO_WAVE>(f);
 }
 
 // Wave p adjusts camera p: points pt_start[p] .. pt_start[p + 1] of X (3 doubles), xn, wt (2 doubles; wt may be null:
@@ -185,147 +162,86 @@ __global__ __launch_bounds__(PO_WAVE) void k_poseadjust(const int64_t *__restric
         used[g] = u ? 1 : 0;
         if (u) { cnt += 1.0; first = g < first ? (long long)g : first; }
     }
-    const int n = (int)po_wave_sum(cnt);
-    first = po_wave_min(first);
+    const int n = (int)grp_sum<PO_WAVE>(cnt);
+    first = grp_min<PO_WAVE>(first);
+
+    // ---- too few ----------------------------------------------------------------------------------------------------------
     const double nan = __builtin_nan("");
     if (n < PO_MIN_POINTS) {                              // the same in every lane
-        if (lane == 0) {
-            dstat[4 * (int64_t)p] = nan; dstat[4 * (int64_t)p + 1] = nan; dstat[4 * (int64_t)p + 2] = nan; dstat[4 * (int64_t)p + 3] = PA_LAMBDA0;
-            istat[4 * (int64_t)p] = PA_TOO_FEW; istat[4 * (int64_t)p + 1] = 0; istat[4 * (int64_t)p + 2] = 0; istat[4 * (int64_t)p + 3] = n;
-        }
+        if (lane == 0) lm_store_too_few(dstat, istat, p, n);
         if (lane < 36) Q[36 * (int64_t)p + lane] = nan;
         if (res)
             for (int64_t g = g0 + lane; g < g1; g += PO_WAVE) { res[2 * g] = 0.0; res[2 * g + 1] = 0.0; }
         return;
     }
-    // the origin: the first used point; the centre -R' t relative to it
+
+    // ---- the origin: the first used point; the centre -R' t relative to it ------------------------------------------------
 #pragma unroll
     for (int k = 0; k < 3; ++k) O[k] = X[3 * first + k];
 #pragma unroll
     for (int k = 0; k < 3; ++k) C[k] = -(R[3 * k] * t[0] + R[3 * k + 1] * t[1] + R[3 * k + 2] * t[2]) - O[k];
-    pa_orthonormalise(R, G, T);
+    dd_orthonormalise(R, G, T);
 
-    // the objective at the start
-    PaDD fsum = {0.0, 0.0};
-    for (int64_t g = g0 + lane; g < g1; g += PO_WAVE) {
-        if (!used[g]) continue;
-        const double Xg[3] = {X[3 * g], X[3 * g + 1], X[3 * g + 2]}, m[2] = {xn[2 * g], xn[2 * g + 1]};
-        const double w[2] = {wt ? wt[2 * g] : 1.0, wt ? wt[2 * g + 1] : 1.0};
-        PaDD Y[3], rr[2];
-        po_residuals(R, C, O, Xg, m, w, Y, rr);
-        fsum = pa_dd_add(fsum, pa_dd_mul(rr[0], rr[0]));
-        fsum = pa_dd_add(fsum, pa_dd_mul(rr[1], rr[1]));
-    }
-    PaDD f = po_wave_sum_dd(fsum);
-    const double f0 = f.hi, floor_f = PA_FLOOR * 2.0 * (double)n;
-    double lambda = PA_LAMBDA0;
-    int iters = 0, trials = 0, code = PA_MAX_ITER;
+    // ---- the objective at the start ---------------------------------------------------------------------------------------
+    double behind;                                        // (none: the selection left those out)
+    LmState lm = lm_start(po_objective(R, C, O, g0, g1, lane, X, xn, wt, used, behind));
+    const double f0 = lm.f.hi, floor_f = LM_FLOOR * 2.0 * (double)n;
     bool fresh = false;                                   // acc holds the sums at (R, C)
     double acc[PO_NSUM];
 
     // ---- the damped loop ------------------------------------------------------------------------------------------------
-    const int max_trials = PA_MAX_REJECT * max_iter;
+    const int max_trials = LM_MAX_REJECT * max_iter;
     for (int trial = 0; trial < max_trials; ++trial) {
-        if (!fresh) { po_linearise(R, C, O, g0, g1, lane, X, xn, wt, used, acc); fresh = true; }
+        if (!fresh) { po_linearise<false>(R, C, O, g0, g1, lane, X, xn, wt, used, nullptr, acc); fresh = true; }
         double S[21], dp[6];
 #pragma unroll
         for (int i = 0; i < 21; ++i) S[i] = acc[i];
 #pragma unroll
-        for (int a = 0; a < 6; ++a) { S[po_s6(a, a)] = acc[po_s6(a, a)] + lambda * acc[po_s6(a, a)]; dp[a] = acc[21 + a]; }
-        bool ok = po_chol6(S, 0.0);
-        po_solve6(S, dp);
+        for (int a = 0; a < 6; ++a) { S[sym_ix<6>(a, a)] = acc[sym_ix<6>(a, a)] + lm.lambda * acc[sym_ix<6>(a, a)]; dp[a] = acc[21 + a]; }
+        bool ok = sym_chol<6>(S, 0.0);
+        sym_solve<6>(S, dp);
         double q = 0.0;
 #pragma unroll
         for (int a = 0; a < 6; ++a) { dp[a] = -dp[a]; q -= acc[21 + a] * dp[a]; ok = ok && (dp[a] - dp[a] == 0.0); }
-        trials += 1;
-        if (f.hi <= floor_f || (ok && q <= tol2 * f.hi)) { code = PA_CONVERGED; break; }
-        bool accept = false;
+        lm = lm_converged(lm, ok, q, floor_f, tol2);
+        if (lm.stop) break;                               // before the trial's objective is paid for
         double Rn[18], Cn[3];
-        PaDD ft = {0.0, 0.0};
+        Dd ft = {0.0, 0.0};
+        double nbad = 0.0;
         if (ok) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) Cn[k] = C[k] + dp[k];
-            pa_rotate_dd(dp + 3, R, Rn, G, T);
-            double nbad = 0.0;
-            for (int64_t g = g0 + lane; g < g1; g += PO_WAVE) {
-                if (!used[g]) continue;
-                const double Xg[3] = {X[3 * g], X[3 * g + 1], X[3 * g + 2]}, m[2] = {xn[2 * g], xn[2 * g + 1]};
-                const double w[2] = {wt ? wt[2 * g] : 1.0, wt ? wt[2 * g + 1] : 1.0};
-                PaDD Y[3], rr[2];
-                po_residuals(Rn, Cn, O, Xg, m, w, Y, rr);
-                ft = pa_dd_add(ft, pa_dd_mul(rr[0], rr[0]));
-                ft = pa_dd_add(ft, pa_dd_mul(rr[1], rr[1]));
-                if (!(Y[2].hi < 0.0)) nbad += 1.0;
-            }
-            ft = po_wave_sum_dd(ft);
-            nbad = po_wave_sum(nbad);
-            accept = nbad == 0.0 && (ft.hi - ft.hi == 0.0) && pa_dd_less(ft, f);
+            dd_rotate_dd(dp + 3, R, Rn, G, T);
+            ft = po_objective(Rn, Cn, O, g0, g1, lane, X, xn, wt, used, nbad);
         }
+        const bool accept = lm_accept(lm, ok, nbad, ft);
         if (accept) {
 #pragma unroll
             for (int i = 0; i < 18; ++i) R[i] = Rn[i];
 #pragma unroll
             for (int k = 0; k < 3; ++k) C[k] = Cn[k];
-            f = ft; lambda = fmax(lambda / 10.0, PA_LAMBDA_MIN); iters += 1; fresh = false;
-            if (iters >= max_iter) { code = PA_MAX_ITER; break; }
-        } else {
-            lambda = lambda * 10.0;
-            if (lambda > PA_LAMBDA_MAX) { code = PA_NO_STEP; break; }
+            fresh = false;
         }
+        lm = lm_step(lm, accept, ft, max_iter);
+        if (lm.stop) break;
     }
 
     // ---- the end: the residuals of every finite point, the undamped matrix at the returned values, its inverse ---------
-#pragma unroll
-    for (int i = 0; i < PO_NSUM; ++i) acc[i] = 0.0;
-    for (int64_t g = g0 + lane; g < g1; g += PO_WAVE) {
-        const bool u = used[g] != 0;
-        if (!u && !res) continue;
-        const double Xg[3] = {X[3 * g], X[3 * g + 1], X[3 * g + 2]}, m[2] = {xn[2 * g], xn[2 * g + 1]};
-        const double w[2] = {wt ? wt[2 * g] : 1.0, wt ? wt[2 * g + 1] : 1.0};
-        PaDD Y[3], rr[2];
-        po_residuals(R, C, O, Xg, m, w, Y, rr);
-        if (res) {
-            const bool fin = (rr[0].hi - rr[0].hi == 0.0) && (rr[1].hi - rr[1].hi == 0.0);
-            res[2 * g] = fin ? rr[0].hi : 0.0; res[2 * g + 1] = fin ? rr[1].hi : 0.0;
-        }
-        if (!u) continue;
-        const double Yh[3] = {Y[0].hi, Y[1].hi, Y[2].hi};
-        double A[12];
-        po_jacobian(R, Yh, w, A);
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int c = a; c < 6; ++c) acc[po_s6(a, c)] += A[a] * A[c] + A[6 + a] * A[6 + c];
-    }
-    double S[21];
-#pragma unroll
-    for (int i = 0; i < 21; ++i) S[i] = po_wave_sum(acc[i]);
-    bool singular = !po_chol6(S, PO_PIVOT);
+    po_linearise<true>(R, C, O, g0, g1, lane, X, xn, wt, used, res, acc);
     double Qc[36];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        double e[6];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) e[r] = r == c ? 1.0 : 0.0;
-        po_solve6(S, e);
-#pragma unroll
-        for (int r = 0; r < 6; ++r) { Qc[6 * c + r] = e[r]; singular = singular || !(e[r] - e[r] == 0.0); }
-    }
+    bool singular = !sym_chol<6>(acc, LM_PIVOT);
+    singular = sym_inverse<6>(acc, Qc) || singular;
     if (lane == 0) {
         double *Qp = Q + 36 * (int64_t)p;
 #pragma unroll
         for (int i = 0; i < 36; ++i) Qp[i] = singular ? nan : Qc[i];
-        if (code == PA_CONVERGED && singular) code = PA_SINGULAR;
 #pragma unroll
         for (int i = 0; i < 9; ++i) Pp[i] = R[i];
         // t = -R C with C = O + (C - O): the two products apart, so that the small one keeps its digits
 #pragma unroll
         for (int r = 0; r < 3; ++r)
             Pp[9 + r] = -((R[r] * O[0] + R[3 + r] * O[1] + R[6 + r] * O[2]) + (R[r] * C[0] + R[3 + r] * C[1] + R[6 + r] * C[2]));
-        dstat[4 * (int64_t)p] = f0; dstat[4 * (int64_t)p + 1] = f.hi;
-        dstat[4 * (int64_t)p + 2] = n > 3 ? sqrt(f.hi / (double)(2 * n - 6)) : nan;
-        dstat[4 * (int64_t)p + 3] = lambda;
-        istat[4 * (int64_t)p] = code; istat[4 * (int64_t)p + 1] = iters; istat[4 * (int64_t)p + 2] = trials; istat[4 * (int64_t)p + 3] = n;
+        lm_store_stats(dstat, istat, p, f0, lm, singular, n, 2 * n - 6);
     }
 }
 
